@@ -274,7 +274,8 @@ WAIT_DEFAULT, WAIT_POLL, WAIT_NAP, WAIT_BLOCK = 0, 1, 2, 3
 class GpuOptions(C.Structure):
     # hso_gpu_options (include/hso_gpu.h): per-context kernel-shape / wait choices; zero = default
     _fields_ = [("size", C.c_int32), ("wait_mode", C.c_int32), ("track_no_coop", C.c_int32), ("track_coop_scatter", C.c_int32),
-                ("track_coop_feats_per_wg", C.c_int32), ("track_coop_workgroups", C.c_int32), ("reserved", C.c_int32 * 2)]
+                ("track_coop_feats_per_wg", C.c_int32), ("track_coop_workgroups", C.c_int32), ("reserved", C.c_int32 * 2),
+                ("eager_gradients", C.c_int32)]
 
 
 class HsoGpuError(RuntimeError):
@@ -320,6 +321,8 @@ def load():
     lib.hso_gpu_frame_release_batch.argtypes = [vp, vp, i32]
     lib.hso_gpu_frame_download_level.argtypes = [vp, i64, i32, vp, P(i32), P(i32)]
     lib.hso_gpu_frame_download_sobel.argtypes = [vp, i64, i32, vp, vp]
+    lib.hso_gpu_debug_sobel_taps.argtypes = [vp, i64, i32, vp, vp]
+    lib.hso_gpu_debug_frame_stats.argtypes = [vp, i64, P(FrameStats)]
     lib.hso_gpu_make_depth_ref.argtypes = [vp, vp, i32, vp, i32, P(SE3), vp]
     lib.hso_gpu_coarse_track_batch.argtypes = [vp, P(Camera), P(TrackParams), P(TrackJob), i32, P(TrackResult)]
     lib.hso_gpu_coarse_track_prepare.argtypes = [vp, P(Camera), P(TrackParams), P(TrackJob), i32]
@@ -409,7 +412,7 @@ EXPORTED_SYMBOLS = [
 
 # ... and every symbol include/hso_gpu_debug.h declares (parity / trace read-backs, developer probes: not part of the boundary)
 DEBUG_SYMBOLS = ["hso_gpu_debug_census", "hso_gpu_klt_debug_level", "hso_gpu_seq_debug_list", "hso_gpu_seq_debug_ref_table", "hso_gpu_debug_fetch",
-                 "hso_gpu_seqmap_debug_dump", "hso_gpu_seq_ba_debug_window"]
+                 "hso_gpu_seqmap_debug_dump", "hso_gpu_seq_ba_debug_window", "hso_gpu_debug_sobel_taps", "hso_gpu_debug_frame_stats"]
 
 
 def select_octree(keys, width, height, n_features):
@@ -470,10 +473,12 @@ class Context:
     def synchronize(self):
         self._check(self.lib.hso_gpu_synchronize(self.h), "synchronize")
 
-    def configure(self, wait_mode=0, track_no_coop=False, track_coop_scatter=False, track_coop_feats_per_wg=0, track_coop_workgroups=0):
+    def configure(self, wait_mode=0, track_no_coop=False, track_coop_scatter=False, track_coop_feats_per_wg=0, track_coop_workgroups=0,
+                  eager_gradients=False):
         """hso_gpu_configure: the context's kernel-shape / wait choices (every call sets all of them; no arguments = the defaults)"""
         o = GpuOptions(C.sizeof(GpuOptions), int(wait_mode), int(bool(track_no_coop)), int(bool(track_coop_scatter)), int(track_coop_feats_per_wg),
                        int(track_coop_workgroups))
+        o.eager_gradients = int(bool(eager_gradients))
         self._check(self.lib.hso_gpu_configure(self.h, C.byref(o)), "configure")
 
     def device_cpulist(self):
@@ -579,6 +584,20 @@ class Context:
         gy = np.empty_like(gx)
         self._check(self.lib.hso_gpu_frame_download_sobel(self.h, frame_id, level, _ptr(gx), _ptr(gy)),
                     "frame_download_sobel")
+        return gx, gy
+
+    def debug_frame_stats(self, frame_id):
+        """hso_gpu_debug_frame_stats: the frame's statistics record as it stands on the device"""
+        st = FrameStats()
+        self._check(self.lib.hso_gpu_debug_frame_stats(self.h, frame_id, C.byref(st)), "debug_frame_stats")
+        return st
+
+    def debug_sobel_taps(self, frame_id, level, w0, h0):
+        """hso_gpu_debug_sobel_taps: (gx, gy), int16 [4, h, w] each; plane 2 * dy + dx at (y, x) = the on-the-fly tap at (x + dx, y + dy)"""
+        lw, lh = self.level_dims(w0, h0, level)
+        gx = np.empty((4, lh, lw), np.int16)
+        gy = np.empty_like(gx)
+        self._check(self.lib.hso_gpu_debug_sobel_taps(self.h, frame_id, level, _ptr(gx), _ptr(gy)), "debug_sobel_taps")
         return gx, gy
 
     # -- tracker

@@ -40,6 +40,10 @@ struct FrameRec {
   int64_t id;
   PyrGeom g;
   uint8_t* base;  // device
+  // the gradient images at sob_off hold THIS frame's gradients.  False after a lazy build (the default: pyramid + statistics only)
+  // and after a refresh in place; hso_frame_require_gradients writes them when a consumer needs them.  The flag belongs to the
+  // record, not to the allocation: a recycled allocation's images are another frame's.
+  bool grad_ready = false;
 };
 
 struct TrackBatchState;  // hso_tracker.hip
@@ -162,10 +166,17 @@ inline size_t hso_grown(size_t need) { return need + need / 2 + (size_t(1) << 20
 char* hso_pinned(hso_gpu_ctx* ctx, int slot, size_t bytes);
 
 
-// frame kernels (hso_frame.hip): build pyramid + Sobel + stats for `n` frames whose
-// level-0 bytes are already in place at base+off[0].
+// frame kernels (hso_frame.hip): build pyramid + stats for `n` frames whose level-0 bytes are already in place at base+off[0].
+// eager: also write the Sobel images of levels 0..2 in the same pass (hso_gpu_options.eager_gradients); otherwise they are
+// written by hso_frame_store_gradients when somebody asks (hso_frame_require_gradients).
 int hso_frame_build(hso_gpu_ctx* ctx, const PyrGeom& g, uint8_t* const* d_bases, const uint8_t* const* d_srcs,
-                    hso_frame_stats* d_stats, int n);
+                    hso_frame_stats* d_stats, int n, bool eager);
+int hso_frame_store_gradients(hso_gpu_ctx* ctx, const PyrGeom& g, uint8_t* const* d_bases, int n);
+// hso_ctx.hip: the Sobel images of the named resident frames exist once the work queued on ctx->stream so far has run — one
+// batched launch per geometry for those that have none yet, nothing otherwise; ids that are not resident are skipped (the caller
+// reports them).  Every host entry point whose kernels read gradient images calls it first.  Uses ctx->d_batch; never waits on the
+// steady path.
+int hso_frame_require_gradients(hso_gpu_ctx* ctx, const int64_t* frame_ids, int n);
 // cv::resize INTER_LINEAR of a device image into a device buffer (hso_frame.hip)
 int hso_frame_resize_into(hso_gpu_ctx* ctx, const uint8_t* d_src, int sw, int sh, uint8_t* d_dst, int dw, int dh);
 void hso_track_state_free(hso_gpu_ctx* ctx);

@@ -365,6 +365,46 @@ void hso_gpu_destroy(hso_gpu_ctx* ctx)
   delete ctx;
 }
 
+// see hso_ctx.h
+extern "C++" int hso_frame_require_gradients(hso_gpu_ctx* ctx, const int64_t* frame_ids, int n)
+{
+  std::vector<FrameRec*> todo;
+  for (int i = 0; i < n; i++) {
+    auto it = ctx->frames.find(frame_ids[i]);
+    if (it == ctx->frames.end() || it->second.grad_ready) continue;
+    it->second.grad_ready = true;   // (also: an id named twice is listed once)
+    todo.push_back(&it->second);
+  }
+  if (todo.empty()) return HSO_OK;
+  auto undo = [&]() { for (FrameRec* r : todo) r->grad_ready = false; };
+  if (hipError_t e = hipSetDevice(ctx->device)) { undo(); HSO_HIP_CHECK(ctx, e); }
+  // frames of one geometry next to each other: one launch each
+  std::stable_sort(todo.begin(), todo.end(), [](const FrameRec* a, const FrameRec* b) { return geom_key(a->g) < geom_key(b->g); });
+  const size_t need = todo.size() * sizeof(uint8_t*);
+  if (ctx->batch_cap < need) {   // (only ever the first call of a context: every batched entry point sizes this area for more)
+    hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) {
+      if (ctx->d_batch) (void)hipFree(ctx->d_batch);
+      ctx->d_batch = nullptr; ctx->batch_cap = 0;
+      e = hipMalloc(reinterpret_cast<void**>(&ctx->d_batch), hso_grown(need));
+    }
+    if (e != hipSuccess) { undo(); HSO_HIP_CHECK(ctx, e); }
+    ctx->batch_cap = hso_grown(need);
+  }
+  std::vector<uint8_t*> bases(todo.size());
+  for (size_t i = 0; i < todo.size(); i++) bases[i] = todo[i]->base;
+  uint8_t** d_bases = reinterpret_cast<uint8_t**>(ctx->d_batch);
+  hipError_t e = hipMemcpyAsync(d_bases, bases.data(), need, hipMemcpyHostToDevice, ctx->stream);   // staged now: `bases` may go
+  if (e != hipSuccess) { undo(); HSO_HIP_CHECK(ctx, e); }
+  for (size_t i0 = 0; i0 < todo.size();) {
+    size_t i1 = i0 + 1;
+    while (i1 < todo.size() && same_geom(todo[i1]->g, todo[i0]->g)) i1++;
+    if (int rc = hso_frame_store_gradients(ctx, todo[i0]->g, d_bases + i0, (int)(i1 - i0))) { undo(); return rc; }
+    i0 = i1;
+  }
+  return HSO_OK;
+}
+
 extern "C++" char* hso_pinned(hso_gpu_ctx* ctx, int slot, size_t bytes)
 {
   if (ctx->h_pin_cap[slot] >= bytes && ctx->h_pin[slot]) return ctx->h_pin[slot];
@@ -510,7 +550,8 @@ int hso_gpu_configure(hso_gpu_ctx* ctx, const hso_gpu_options* o)
   if (!o || o->size < (int32_t)(4 * sizeof(int32_t)) || o->size > (int32_t)sizeof(hso_gpu_options)) return hso_fail(ctx, HSO_E_INVALID, "configure: options missing or of an unknown size");
   hso_gpu_options n{};
   memcpy(&n, o, (size_t)o->size);
-  if (n.wait_mode < HSO_WAIT_DEFAULT || n.wait_mode > HSO_WAIT_BLOCK || n.track_coop_feats_per_wg < 0 || n.track_coop_workgroups < 0)
+  if (n.wait_mode < HSO_WAIT_DEFAULT || n.wait_mode > HSO_WAIT_BLOCK || n.track_coop_feats_per_wg < 0 || n.track_coop_workgroups < 0 ||
+      n.eager_gradients < 0 || n.eager_gradients > 1)
     return hso_fail(ctx, HSO_E_INVALID, "configure: value out of range");
   ctx->opt = n;
   hso_apply_wait_mode(ctx);
@@ -547,7 +588,8 @@ int hso_gpu_frame_upload(hso_gpu_ctx* ctx, int64_t frame_id, const uint8_t* img,
   // the kernels take a device array of frame base pointers (batched form); one entry here
   uint8_t** d_bases = reinterpret_cast<uint8_t**>(rec.base + rec.g.stats_off + 128);
   HSO_FRAME_TRY(ctx, rec.g, rec.base, hipMemcpyAsync(d_bases, &rec.base, sizeof(uint8_t*), hipMemcpyHostToDevice, ctx->stream));
-  int rc = hso_frame_build(ctx, rec.g, d_bases, nullptr, nullptr, 1);
+  rec.grad_ready = ctx->opt.eager_gradients != 0;
+  int rc = hso_frame_build(ctx, rec.g, d_bases, nullptr, nullptr, 1, rec.grad_ready);
   if (rc < 0) { (void)hipStreamSynchronize(ctx->stream); hso_frame_free(ctx, rec.g, rec.base); return rc; }
   if (stats_out) {
     HSO_FRAME_TRY(ctx, rec.g, rec.base, hipMemcpyAsync(stats_out, rec.base + rec.g.stats_off, sizeof(hso_frame_stats),
@@ -590,7 +632,8 @@ int hso_gpu_frame_upload_resized(hso_gpu_ctx* ctx, int64_t frame_id, const uint8
   if (rc < 0) { (void)hipStreamSynchronize(ctx->stream); hso_frame_free(ctx, rec.g, rec.base); return rc; }
   uint8_t** d_bases = reinterpret_cast<uint8_t**>(rec.base + rec.g.stats_off + 128);
   HSO_FRAME_TRY(ctx, rec.g, rec.base, hipMemcpyAsync(d_bases, &rec.base, sizeof(uint8_t*), hipMemcpyHostToDevice, ctx->stream));
-  rc = hso_frame_build(ctx, rec.g, d_bases, nullptr, nullptr, 1);
+  rec.grad_ready = ctx->opt.eager_gradients != 0;
+  rc = hso_frame_build(ctx, rec.g, d_bases, nullptr, nullptr, 1, rec.grad_ready);
   if (rc < 0) { (void)hipStreamSynchronize(ctx->stream); hso_frame_free(ctx, rec.g, rec.base); return rc; }
   if (stats_out)
     HSO_FRAME_TRY(ctx, rec.g, rec.base, hipMemcpyAsync(stats_out, rec.base + rec.g.stats_off, sizeof(hso_frame_stats), hipMemcpyDeviceToHost, ctx->stream));
@@ -623,7 +666,10 @@ int hso_gpu_frame_upload_batch(hso_gpu_ctx* ctx, const int64_t* frame_ids, const
   auto undo = [&]() { hso_stream_abandon(ctx->stream); for (int i : fresh) hso_frame_free(ctx, g, bases[i]); };
   for (int i = 0; i < n; i++) {
     auto it = ctx->frames.find(frame_ids[i]);
-    if (it != ctx->frames.end()) { bases[i] = it->second.base; continue; }   // refresh in place
+    if (it != ctx->frames.end()) {   // refresh in place: from here on the gradient images are no longer this frame's
+      bases[i] = it->second.base; it->second.grad_ready = false;
+      continue;
+    }
     if (int rc = hso_frame_alloc(ctx, g, &bases[i])) { undo(); return rc; }
     fresh.push_back(i);
   }
@@ -647,7 +693,8 @@ int hso_gpu_frame_upload_batch(hso_gpu_ctx* ctx, const int64_t* frame_ids, const
     for (int i = 0; i < n; i++)
       HSO_BATCH_TRY(hipMemcpyAsync(bases[i] + g.off[0], imgs[i], (size_t)width * height, hipMemcpyHostToDevice, ctx->stream));
   }
-  int rc = hso_frame_build(ctx, g, d_bases, img_is_device ? d_srcs : nullptr, stats_out ? d_stats : nullptr, n);
+  const bool eager = ctx->opt.eager_gradients != 0;
+  int rc = hso_frame_build(ctx, g, d_bases, img_is_device ? d_srcs : nullptr, stats_out ? d_stats : nullptr, n, eager);
   if (rc < 0) { undo(); return rc; }
   if (stats_out) {
     HSO_BATCH_TRY(hipMemcpyAsync(stats_out, d_stats, (size_t)n * sizeof(hso_frame_stats), hipMemcpyDeviceToHost, ctx->stream));
@@ -659,6 +706,7 @@ int hso_gpu_frame_upload_batch(hso_gpu_ctx* ctx, const int64_t* frame_ids, const
     rec.id = frame_ids[i]; rec.g = g; rec.base = bases[i];
     ctx->frames[frame_ids[i]] = rec;
   }
+  for (int i = 0; i < n; i++) ctx->frames[frame_ids[i]].grad_ready = eager;
   return HSO_OK;
 }
 
@@ -719,10 +767,22 @@ int hso_gpu_frame_download_sobel(hso_gpu_ctx* ctx, int64_t frame_id, int level, 
   if (level < 0 || level >= HSO_N_SOBEL_LEVELS) return hso_fail(ctx, HSO_E_INVALID, "download_sobel: bad level");
   auto it = ctx->frames.find(frame_id);
   if (it == ctx->frames.end()) return hso_fail(ctx, HSO_E_NOFRAME, "download_sobel: frame not resident");
+  if (int rc = hso_frame_require_gradients(ctx, &frame_id, 1)) return rc;
   const PyrGeom& g = it->second.g;
   const size_t row = (size_t)g.w[level] * 2, pitch = (size_t)g.sob_stride[level] * 2;   // rows are padded to 128-byte lines on the device
   HSO_HIP_CHECK(ctx, hipMemcpy2DAsync(gx, row, it->second.base + g.sob_off[level][0], pitch, row, (size_t)g.h[level], hipMemcpyDeviceToHost, ctx->stream));
   HSO_HIP_CHECK(ctx, hipMemcpy2DAsync(gy, row, it->second.base + g.sob_off[level][1], pitch, row, (size_t)g.h[level], hipMemcpyDeviceToHost, ctx->stream));
+  HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return HSO_OK;
+}
+
+// include/hso_gpu_debug.h
+int hso_gpu_debug_frame_stats(hso_gpu_ctx* ctx, int64_t frame_id, hso_frame_stats* out)
+{
+  if (!ctx || !out) return HSO_E_INVALID;
+  auto it = ctx->frames.find(frame_id);
+  if (it == ctx->frames.end()) return hso_fail(ctx, HSO_E_NOFRAME, "debug_frame_stats: frame not resident");
+  HSO_HIP_CHECK(ctx, hipMemcpyAsync(out, it->second.base + it->second.g.stats_off, sizeof(hso_frame_stats), hipMemcpyDeviceToHost, ctx->stream));
   HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return HSO_OK;
 }

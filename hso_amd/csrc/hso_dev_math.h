@@ -383,4 +383,35 @@ HSO_DEV T wave_sum_to_lane63(T v)
   return v;
 }
 
+// ---- 5x5 Sobel at single pixels ----
+// cv::Sobel(CV_16S, ksize 5, BORDER_REPLICATE) of a u8 level (row stride = W) at the four integer pixels (x, y), (x + 1, y),
+// (x, y + 1), (x + 1, y + 1), from their common 6x6 window: derivative [-1 -2 0 2 1], smoothing [1 4 6 4 1], exact integers
+// (|value| <= 24480) — the values k_sobel (hso_frame.hip) writes into a frame's gradient images at those pixels, bit for bit, so
+// that a kernel that needs a handful of taps (Matcher::checkNormal) does not need the images.  gx[2 * dy + dx], gy likewise.
+// Coordinates are clamped to the level, so any (x, y) reads defined bytes.
+HSO_DEV void sobel5_taps4(const uint8_t* img, int W, int H, int x, int y, int (&gx)[4], int (&gy)[4])
+{
+  int hd[6][2], hs[6][2];
+#pragma unroll
+  for (int r = 0; r < 6; r++) {
+    const int yy = min(max(y - 2 + r, 0), H - 1);
+    const uint8_t* row = img + (size_t)yy * W;
+    int p[6];
+#pragma unroll
+    for (int c = 0; c < 6; c++) p[c] = row[min(max(x - 2 + c, 0), W - 1)];
+#pragma unroll
+    for (int dx = 0; dx < 2; dx++) {
+      hd[r][dx] = (p[dx + 4] - p[dx]) + 2 * (p[dx + 3] - p[dx + 1]);
+      hs[r][dx] = (p[dx] + p[dx + 4]) + 4 * (p[dx + 1] + p[dx + 3]) + 6 * p[dx + 2];
+    }
+  }
+#pragma unroll
+  for (int dy = 0; dy < 2; dy++)
+#pragma unroll
+    for (int dx = 0; dx < 2; dx++) {
+      gx[2 * dy + dx] = (hd[dy][dx] + hd[dy + 4][dx]) + 4 * (hd[dy + 1][dx] + hd[dy + 3][dx]) + 6 * hd[dy + 2][dx];
+      gy[2 * dy + dx] = (hs[dy + 4][dx] - hs[dy][dx]) + 2 * (hs[dy + 3][dx] - hs[dy + 1][dx]);
+    }
+}
+
 }  // namespace hso_dev

@@ -445,6 +445,9 @@ static int detect_candidates_impl(hso_gpu_ctx* ctx, const int64_t* frame_ids, in
   }
   auto it0 = ctx->frames.find(frame_ids[0]);
   if (it0 == ctx->frames.end()) return hso_fail(ctx, HSO_E_NOFRAME, "detect_candidates: frame not resident");
+  // k_canny_nms and k_edgelet_cells read the Sobel images of every level: frames that were built without them get them now, in front
+  // of the kernels below on the same stream.  (The initialisation entry, hso_gpu_detect_candidates_init, reads no gradient image.)
+  if (int rc = hso_frame_require_gradients(ctx, frame_ids, n_frames)) return rc;
   const PyrGeom g = it0->second.g;
   auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
   // extra area: [have flags of every frame | pass flags] (one memset), edgelet totals, then the frame slices

@@ -9,9 +9,14 @@
 // two means, which the reference accumulates serially in fp32 and this kernel
 // accumulates exactly (integer) / in fp64 with a fixed reduction tree.
 //
-// Roofline: HBM-bound.  Per frame W*H bytes are read once for the pyramid
-// (1.33*W*H written), levels 0-2 are read once more for Sobel (1.31*W*H) and
-// 5.25*W*H bytes of int16 gradients are written.
+// Roofline.  Per frame W*H bytes are read once for the pyramid (1.33*W*H written) and level 0
+// is read once more (W*H) for the statistics, which need every level-0 gradient magnitude but
+// no gradient image: that pass (k_sobel<.., SOB_STATS>) stores 16 bytes per block and is bound by
+// its arithmetic (VALU issue), not by HBM.  The int16 gradient images of levels 0-2 (5.25*W*H
+// bytes written, 1.31*W*H read; HBM-bound) are written only for frames a gradient reader names
+// (candidate detection on keyframes, the Sobel download): hso_frame_require_gradients ->
+// k_sobel<.., SOB_STORE>; or with every build when hso_gpu_options.eager_gradients is set
+// (k_sobel<.., SOB_BOTH>, one pass for both products).
 #include "hso_ctx.h"
 #include "hso_dev_math.h"
 
@@ -173,6 +178,7 @@ int hso_frame_resize_into(hso_gpu_ctx* ctx, const uint8_t* d_src, int sw, int sh
 #define SOB_TW 64              // wavefront tile: 16 lanes x 4 pixels wide,
 #define SOB_TH (4 * SOB_STRIP) //                 4 lane groups x SOB_STRIP rows high (60: divides 480, 240, 120)
 #define SOB_WAVES 4            // tiles (wavefronts) per block
+enum { SOB_BOTH = 0, SOB_STATS = 1, SOB_STORE = 2 };   // k_sobel's MODE
 
 typedef const __attribute__((address_space(1))) uint8_t* SobGlbCU8;
 typedef const __attribute__((address_space(1))) uint32_t* SobGlbCU32;
@@ -184,7 +190,7 @@ typedef __attribute__((address_space(1))) unsigned long long* SobGlbU64;
 // loads of row i + PF issued before row i is worked on.  Same arithmetic as the general strip inside k_sobel<false>.
 // Measured on 4096 EuRoC frames (rocprofv3, profiles/r4_sobel_variants.md): PF 0 / 1 / 2 / 3 / 4 = 2.41 / 2.30 / 2.31 /
 // 2.39 / 2.40 ms at 54 / 61 / 65 / 69 / 72 VGPRs; all 57 loads at the top (82 VGPRs) 2.79 ms; the general kernel 2.50 ms.
-template <int PF>
+template <int PF, int MODE>
 HSO_DEV void sobel_strip(const SobGlbCU8 img, const SobGlbI16 gx, const SobGlbI16 gy, const int W, const int H, const int GS,
                          const int level, const int x, const int ys, unsigned& isum, double& gsum)
 {
@@ -252,9 +258,11 @@ HSO_DEV void sobel_strip(const SobGlbCU8 img, const SobGlbI16 gx, const SobGlbI1
         sy0.v = (hs[re][0] - hs[ra][0]) + k2 * (hs[rd][0] - hs[rb][0]);
         sy1.v = (hs[re][1] - hs[ra][1]) + k2 * (hs[rd][1] - hs[rb][1]);
         typedef unsigned long long u64;
-        __builtin_nontemporal_store(((u64)sx1.u << 32) | sx0.u, (GlbU64)(gx + (size_t)y * GS + x));
-        __builtin_nontemporal_store(((u64)sy1.u << 32) | sy0.u, (GlbU64)(gy + (size_t)y * GS + x));
-        if (level == 0 && x >= 16 && x < W - 16 && y >= 16 && y < H - 16) {
+        if (MODE != SOB_STATS) {
+          __builtin_nontemporal_store(((u64)sx1.u << 32) | sx0.u, (GlbU64)(gx + (size_t)y * GS + x));
+          __builtin_nontemporal_store(((u64)sy1.u << 32) | sy0.u, (GlbU64)(gy + (size_t)y * GS + x));
+        }
+        if (MODE != SOB_STORE && level == 0 && x >= 16 && x < W - 16 && y >= 16 && y < H - 16) {
           // |grad| of the four pixels.  gx^2 + gy^2 <= 2 * 24480^2 < 2^31 is formed exactly by one
           // v_dot2_i32_i16 per pixel on the {gx, gy} pair (v_perm_b32 pairs them up), converted once
           // and rooted by the hardware v_sqrt_f32 (1 ulp).  The reference (src/frame.cpp:231) rounds
@@ -292,12 +300,19 @@ HSO_DEV void sobel_strip(const SobGlbCU8 img, const SobGlbI16 gx, const SobGlbI1
 // one full 128-byte line per 16 lanes (the previous LDS version stored 2 bytes per lane).  The
 // strip loop is fully unrolled so the window is indexed statically.
 // ALLFAST: every Sobel level's width is a multiple of 4 (chosen on the host): the pipelined strip above, 61 VGPRs.
-template <bool ALLFAST>
+//
+// MODE (which of the two products a launch makes; the arithmetic, the partition and every sum's order are the same in all three):
+//   SOB_BOTH   gradient images of levels 0..2 and the level-0 partials (an eager build);
+//   SOB_STATS  the level-0 partials only — grid (sobel_blocks[0], frames), no gradient store (the lazy build of every frame: the
+//              statistics need the level-0 magnitudes, nobody needs the images until a frame is searched for edgelets);
+//   SOB_STORE  the gradient images only, levels 0..2 — no magnitudes, no partials (hso_frame_store_gradients, on demand).
+template <bool ALLFAST, int MODE>
 __global__ __launch_bounds__(256) void k_sobel(PyrGeom g, uint8_t* const* bases)
 {
   __shared__ double s_part[4][2];
   int b = blockIdx.x, level = 0;
-  while (level < HSO_N_SOBEL_LEVELS - 1 && b >= g.sobel_blocks[level]) { b -= g.sobel_blocks[level]; level++; }
+  if (MODE != SOB_STATS)
+    while (level < HSO_N_SOBEL_LEVELS - 1 && b >= g.sobel_blocks[level]) { b -= g.sobel_blocks[level]; level++; }
   const int W = g.w[level], H = g.h[level], GS = g.sob_stride[level];
   // pointers read from a table are generic; say "global" so the accesses are global_load / global_store
   // instead of FLAT (which also probes the LDS aperture and ties up both wait counters)
@@ -318,7 +333,7 @@ __global__ __launch_bounds__(256) void k_sobel(PyrGeom g, uint8_t* const* bases)
   unsigned isum = 0;
   double gsum = 0;
   if (ALLFAST) {
-    if (x < W && ys < H) sobel_strip<1>((SobGlbCU8)img, (SobGlbI16)gx, (SobGlbI16)gy, W, H, GS, level, x, ys, isum, gsum);
+    if (x < W && ys < H) sobel_strip<1, MODE>((SobGlbCU8)img, (SobGlbI16)gx, (SobGlbI16)gy, W, H, GS, level, x, ys, isum, gsum);
   } else
   if (x < W && ys < H) {
     // widths that are multiples of 4 (every halfSample pyramid): aligned dwords for every lane; a
@@ -380,7 +395,8 @@ __global__ __launch_bounds__(256) void k_sobel(PyrGeom g, uint8_t* const* bases)
           sy0.v = (hs[re][0] - hs[ra][0]) + k2 * (hs[rd][0] - hs[rb][0]);
           sy1.v = (hs[re][1] - hs[ra][1]) + k2 * (hs[rd][1] - hs[rb][1]);
           typedef unsigned long long u64;
-          if (x + 4 <= W && ((W & 3) == 0)) {
+          if (MODE == SOB_STATS) {
+          } else if (x + 4 <= W && ((W & 3) == 0)) {
             __builtin_nontemporal_store(((u64)sx1.u << 32) | sx0.u, (GlbU64)(gx + (size_t)y * GS + x));
             __builtin_nontemporal_store(((u64)sy1.u << 32) | sy0.u, (GlbU64)(gy + (size_t)y * GS + x));
           } else {  // widths that are not multiples of 4 (cv::resize pyramids): element-wise, last lane clipped
@@ -389,7 +405,7 @@ __global__ __launch_bounds__(256) void k_sobel(PyrGeom g, uint8_t* const* bases)
             for (int k = 0; k < 4; k++)
               if (x + k < W) { gx[(size_t)y * GS + x + k] = sxv[k]; gy[(size_t)y * GS + x + k] = syv[k]; }
           }
-          if (level == 0 && x >= 16 && x < W - 16 && y >= 16 && y < H - 16) {
+          if (MODE != SOB_STORE && level == 0 && x >= 16 && x < W - 16 && y >= 16 && y < H - 16) {
             // |grad| of the four pixels.  gx^2 + gy^2 <= 2 * 24480^2 < 2^31 is formed exactly by one
             // v_dot2_i32_i16 per pixel on the {gx, gy} pair (v_perm_b32 pairs them up), converted once
             // and rooted by the hardware v_sqrt_f32 (1 ulp).  The reference (src/frame.cpp:231) rounds
@@ -413,7 +429,7 @@ __global__ __launch_bounds__(256) void k_sobel(PyrGeom g, uint8_t* const* bases)
       }
     }
   }
-  if (level == 0) {
+  if (MODE != SOB_STORE && level == 0) {
     double is = wave_sum_to_lane63((double)isum);
     double gs = wave_sum_to_lane63(gsum);
     if (lane == 63) { s_part[wv][0] = is; s_part[wv][1] = gs; }
@@ -454,21 +470,37 @@ __global__ __launch_bounds__(64) void k_frame_stats(PyrGeom g, uint8_t* const* b
 #ifndef HSO_FRAME_CHUNK_MB
 #define HSO_FRAME_CHUNK_MB 96   // pyramid levels a chunk of frames leaves for its Sobel pass, in MB (0: one launch pair for the whole batch)
 #endif
-int hso_frame_build(hso_gpu_ctx* ctx, const PyrGeom& g, uint8_t* const* d_bases, const uint8_t* const* d_srcs,
-                    hso_frame_stats* d_stats, int n)
+template <int MODE>
+static void sobel_launch(hso_gpu_ctx* ctx, const PyrGeom& g, uint8_t* const* bases, int m)
 {
-  // Large batches are built in chunks: the Sobel pass re-reads levels 0..2 (1.31 W H bytes per frame) that the pyramid pass has
-  // just written; with both passes over a few hundred frames at a time those bytes come out of the 256 MB Infinity Cache instead
-  // of HBM (4096 EuRoC frames leave 1.9 GB of levels: nothing of it survives to the Sobel pass of a whole-batch launch).  This
-  // is what a fused pyramid + Sobel kernel would save, without its halo bookkeeping (profiles/r6_fused_frame.md).
+  bool all_fast = true;
+  for (int l = 0; l < HSO_N_SOBEL_LEVELS; l++) all_fast = all_fast && (g.w[l] & 3) == 0;
+  const int blocks = MODE == SOB_STATS ? g.sobel_blocks[0] : g.sobel_blocks[0] + g.sobel_blocks[1] + g.sobel_blocks[2];
+  if (all_fast) hipLaunchKernelGGL((k_sobel<true, MODE>), dim3(blocks, m), dim3(256), 0, ctx->stream, g, bases);
+  else hipLaunchKernelGGL((k_sobel<false, MODE>), dim3(blocks, m), dim3(256), 0, ctx->stream, g, bases);
+}
+
+int hso_frame_store_gradients(hso_gpu_ctx* ctx, const PyrGeom& g, uint8_t* const* d_bases, int n)
+{
+  for (int c0 = 0; c0 < n; c0 += 32768)     // blockIdx.y is a 16-bit quantity
+    sobel_launch<SOB_STORE>(ctx, g, d_bases + c0, std::min(32768, n - c0));
+  HSO_HIP_CHECK(ctx, hipGetLastError());
+  return HSO_OK;
+}
+
+int hso_frame_build(hso_gpu_ctx* ctx, const PyrGeom& g, uint8_t* const* d_bases, const uint8_t* const* d_srcs,
+                    hso_frame_stats* d_stats, int n, bool eager)
+{
+  // Large batches are built in chunks: the Sobel pass re-reads what the pyramid pass has just written (level 0, W H bytes per
+  // frame, for the statistics; levels 0..2, 1.31 W H, in an eager build); with both passes over a few hundred frames at a time
+  // those bytes come out of the 256 MB Infinity Cache instead of HBM (4096 EuRoC frames leave 1.9 GB of levels: nothing of it
+  // survives to the Sobel pass of a whole-batch launch).  This is what a fused pyramid + Sobel kernel would save, without its halo
+  // bookkeeping (profiles/r6_fused_frame.md).
   const bool half = (g.w[0] % 16) == 0 && (g.h[0] % 16) == 0;
   const size_t per_frame = (size_t)g.pyr_bytes;
   int chunk = n;
   if (HSO_FRAME_CHUNK_MB > 0 && half && (size_t)n * per_frame > ((size_t)2 * HSO_FRAME_CHUNK_MB << 20))
     chunk = (int)std::max<size_t>(64, ((size_t)HSO_FRAME_CHUNK_MB << 20) / per_frame);
-  const int sob_total = g.sobel_blocks[0] + g.sobel_blocks[1] + g.sobel_blocks[2];
-  bool all_fast = true;
-  for (int l = 0; l < HSO_N_SOBEL_LEVELS; l++) all_fast = all_fast && (g.w[l] & 3) == 0;
   for (int c0 = 0; c0 < n; c0 += chunk) {
     const int m = std::min(chunk, n - c0);
     uint8_t* const* bases = d_bases + c0;
@@ -482,8 +514,8 @@ int hso_frame_build(hso_gpu_ctx* ctx, const PyrGeom& g, uint8_t* const* d_bases,
       for (int l = 1; l < HSO_N_PYR_LEVELS; l++)
         hipLaunchKernelGGL(k_resize_level, dim3((g.w[l] * g.h[l] + 255) / 256, m), dim3(256), 0, ctx->stream, g, bases, l);
     }
-    if (all_fast) hipLaunchKernelGGL(k_sobel<true>, dim3(sob_total, m), dim3(256), 0, ctx->stream, g, bases);
-    else hipLaunchKernelGGL(k_sobel<false>, dim3(sob_total, m), dim3(256), 0, ctx->stream, g, bases);
+    if (eager) sobel_launch<SOB_BOTH>(ctx, g, bases, m);
+    else sobel_launch<SOB_STATS>(ctx, g, bases, m);
   }
   hipLaunchKernelGGL(k_frame_stats, dim3(n), dim3(64), 0, ctx->stream, g, d_bases, d_stats);
   HSO_HIP_CHECK(ctx, hipGetLastError());
@@ -522,4 +554,43 @@ PyrGeom make_geom(int w, int h)
   off += 256;
   g.frame_bytes = off;
   return g;
+}
+
+// ---- hso_gpu_debug_sobel_taps (include/hso_gpu_debug.h): sobel5_taps4 at every pixel of a level, for the parity test against the
+// gradient images.  One thread per window origin; plane k = 2 * dy + dx holds the tap at (x + dx, y + dy).
+__global__ __launch_bounds__(256) void k_debug_sobel_taps(const uint8_t* img, int W, int H, int16_t* gx_out, int16_t* gy_out)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= W * H) return;
+  int gx[4], gy[4];
+  sobel5_taps4(img, W, H, i % W, i / W, gx, gy);
+#pragma unroll
+  for (int k = 0; k < 4; k++) { gx_out[(size_t)k * W * H + i] = (int16_t)gx[k]; gy_out[(size_t)k * W * H + i] = (int16_t)gy[k]; }
+}
+
+extern "C" int hso_gpu_debug_sobel_taps(hso_gpu_ctx* ctx, int64_t frame_id, int level, int16_t* gx, int16_t* gy)
+{
+  if (!ctx || !gx || !gy) return HSO_E_INVALID;
+  if (level < 0 || level >= HSO_N_PYR_LEVELS) return hso_fail(ctx, HSO_E_INVALID, "debug_sobel_taps: bad level");
+  auto it = ctx->frames.find(frame_id);
+  if (it == ctx->frames.end()) return hso_fail(ctx, HSO_E_NOFRAME, "debug_sobel_taps: frame not resident");
+  const PyrGeom& g = it->second.g;
+  const int W = g.w[level], H = g.h[level];
+  const size_t plane4 = (size_t)4 * W * H * sizeof(int16_t), need = 2 * plane4;
+  HSO_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (ctx->batch_cap < need) {
+    HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->d_batch) (void)hipFree(ctx->d_batch);
+    ctx->d_batch = nullptr; ctx->batch_cap = 0;
+    HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_batch), hso_grown(need)));
+    ctx->batch_cap = hso_grown(need);
+  }
+  int16_t* d_gx = reinterpret_cast<int16_t*>(ctx->d_batch);
+  int16_t* d_gy = reinterpret_cast<int16_t*>(ctx->d_batch + plane4);
+  hipLaunchKernelGGL(k_debug_sobel_taps, dim3((W * H + 255) / 256), dim3(256), 0, ctx->stream, it->second.base + g.off[level], W, H, d_gx, d_gy);
+  HSO_HIP_CHECK(ctx, hipGetLastError());
+  HSO_HIP_CHECK(ctx, hipMemcpyAsync(gx, d_gx, plane4, hipMemcpyDeviceToHost, ctx->stream));
+  HSO_HIP_CHECK(ctx, hipMemcpyAsync(gy, d_gy, plane4, hipMemcpyDeviceToHost, ctx->stream));
+  HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return HSO_OK;
 }

@@ -304,8 +304,6 @@ HSO_DEV hso_align_out match_patch(const PyrGeom& g, const uint8_t* cur_base, con
 
   // ---- Matcher::checkNormal, :406-440 (edgelets only)
   if (ok && edgelet) {
-    const int16_t* gx = reinterpret_cast<const int16_t*>(cur_base + g.sob_off[search_level][0]);
-    const int16_t* gy = reinterpret_cast<const int16_t*>(cur_base + g.sob_off[search_level][1]);
     const float uf = (float)pxs0, vf = (float)pxs1;
     // (an LK result is inside the level with a 4-pixel margin by its own loop test, :234; the guard only keeps the read defined)
     const bool inside = uf >= 0 && vf >= 0 && uf < (float)(cols - 1) && vf < (float)(rows - 1);
@@ -315,10 +313,11 @@ HSO_DEV hso_align_out match_patch(const PyrGeom& g, const uint8_t* cur_base, con
     const float wTR = (float)(sx * (1.0 - sy));
     const float wBL = (float)((1.0 - sx) * sy);
     const float wBR = (float)(((1.0 - wTL) - wTR) - wBL);
-    const int gs = g.sob_stride[search_level];   // gradient rows are padded (hso_ctx.h)
-    const int a = vi * gs + ui;
-    double n0 = (((double)wTL * (double)gx[a] + (double)wTR * (double)gx[a + 1]) + (double)wBL * (double)gx[a + gs]) + (double)wBR * (double)gx[a + gs + 1];
-    double n1 = (((double)wTL * (double)gy[a] + (double)wTR * (double)gy[a + 1]) + (double)wBL * (double)gy[a + gs]) + (double)wBR * (double)gy[a + gs + 1];
+    // the four taps of Frame::sobelX_ / sobelY_ (:421-428), formed from the level's pixels: the frame need not carry gradient images
+    int gx[4], gy[4];
+    sobel5_taps4(cur, cols, rows, ui, vi, gx, gy);
+    double n0 = (((double)wTL * (double)gx[0] + (double)wTR * (double)gx[1]) + (double)wBL * (double)gx[2]) + (double)wBR * (double)gx[3];
+    double n1 = (((double)wTL * (double)gy[0] + (double)wTR * (double)gy[1]) + (double)wBL * (double)gy[2]) + (double)wBR * (double)gy[3];
     const double nn = sqrt(n0 * n0 + n1 * n1);
     n0 /= nn; n1 /= nn;
     ok = inside && (dir0 * n0 + dir1 * n1) > (double)(float)0.86;  // Config::edgeLetCosAngle() through a float parameter

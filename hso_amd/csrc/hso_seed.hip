@@ -504,8 +504,6 @@ HSO_DEV bool g_refine(const SeedConsts& C, const uint8_t* cur_base, int sl, int 
     result = g_klt_limited<true>(cur, cols, rows, gxr, gyr, ref_px, dc0, dc1, ps0, ps1, samp, l8);
     if (result) {
       // Matcher::checkNormal(cur_frame, search_level_, px, dir_cur, 0.7), :406-440
-      const int16_t* gx = reinterpret_cast<const int16_t*>(cur_base + C.g.sob_off[sl][0]);
-      const int16_t* gy = reinterpret_cast<const int16_t*>(cur_base + C.g.sob_off[sl][1]);
       const float uf = (float)ps0, vf = (float)ps1;
       // The reference reads the four taps unchecked (:421-428): a NaN position (an edgelet direction of norm 0 lets
       // KLTLimited1D "succeed" with a NaN pixel) or one outside the image is an out-of-bounds read there.  Defined here and in
@@ -517,10 +515,11 @@ HSO_DEV bool g_refine(const SeedConsts& C, const uint8_t* cur_base, int sl, int 
         const float sx = uf - (float)ui, sy = vf - (float)vi;
         const float wTL = (float)((1.0 - sx) * (1.0 - sy)), wTR = (float)(sx * (1.0 - sy)), wBL = (float)((1.0 - sx) * sy);
         const float wBR = (float)(((1.0 - wTL) - wTR) - wBL);
-        const int gs = C.g.sob_stride[sl];
-        const int a = vi * gs + ui;
-        double n0 = (((double)wTL * (double)gx[a] + (double)wTR * (double)gx[a + 1]) + (double)wBL * (double)gx[a + gs]) + (double)wBR * (double)gx[a + gs + 1];
-        double n1 = (((double)wTL * (double)gy[a] + (double)wTR * (double)gy[a + 1]) + (double)wBL * (double)gy[a + gs]) + (double)wBR * (double)gy[a + gs + 1];
+        // the four taps of Frame::sobelX_ / sobelY_ (:421-428), formed from the level's pixels: the frame need not carry gradient images
+        int gx[4], gy[4];
+        sobel5_taps4(cur, cols, rows, ui, vi, gx, gy);
+        double n0 = (((double)wTL * (double)gx[0] + (double)wTR * (double)gx[1]) + (double)wBL * (double)gx[2]) + (double)wBR * (double)gx[3];
+        double n1 = (((double)wTL * (double)gy[0] + (double)wTR * (double)gy[1]) + (double)wBL * (double)gy[2]) + (double)wBR * (double)gy[3];
         const double nn = sqrt(n0 * n0 + n1 * n1);
         n0 /= nn; n1 /= nn;
         result = (dc0 * n0 + dc1 * n1) > (double)(float)0.7;

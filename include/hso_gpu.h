@@ -99,6 +99,10 @@ typedef struct hso_gpu_options {
   int32_t track_coop_feats_per_wg;   /* features per workgroup the cooperative shape aims for (0: 256) */
   int32_t track_coop_workgroups;     /* workgroups per job of the cooperative shape (0: from the feature count) */
   int32_t reserved[2];
+  int32_t eager_gradients;     /* 1: every frame upload also writes the Sobel images of levels 0..2 (one pass with the statistics).
+                                  0 (default): an upload builds pyramid + statistics only and the images of a frame are written the
+                                  first time an entry point that reads them names it (candidate detection, hso_gpu_frame_download_sobel);
+                                  results are the same bits either way.  Takes effect for uploads after the call. */
 } hso_gpu_options;
 int hso_gpu_configure(hso_gpu_ctx* ctx, const hso_gpu_options* options);
 /* The host side of the batched entry points (staging tens of megabytes of local-BA windows, checking and staging map patches) is a

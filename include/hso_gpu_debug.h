@@ -69,6 +69,15 @@ int hso_gpu_seq_ba_debug_window(hso_gpu_ctx* ctx, int job, int what, void* out, 
  * (interleaved Ix, Iy); either output may be NULL */
 int hso_gpu_klt_debug_level(hso_gpu_ctx* ctx, int64_t frame, int level, uint8_t* img_out, int16_t* deriv_out);
 
+/* test hook: the 5x5 Sobel taps the matching kernels form from a level's pixels (Matcher::checkNormal reads four of them per
+ * converged edgelet; frames carry gradient images only once a detection has asked for them), at every pixel of pyramid level
+ * `level` of a resident frame.  gx, gy: int16[4][h][w]; plane k = 2 * dy + dx holds, at (y, x), the gradient at pixel
+ * (x + dx, y + dy) as the device function evaluates it from the window anchored at (x, y) — equal to the gradient image there
+ * wherever x + dx < w and y + dy < h.  Does not create or change the frame's gradient images. */
+int hso_gpu_debug_sobel_taps(hso_gpu_ctx* ctx, int64_t frame, int level, int16_t* gx, int16_t* gy);
+/* test hook: the statistics record a resident frame carries on the device now (what its upload returned, unless something wrote it since) */
+int hso_gpu_debug_frame_stats(hso_gpu_ctx* ctx, int64_t frame, hso_frame_stats* out);
+
 #ifdef __cplusplus
 }
 #endif
