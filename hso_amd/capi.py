@@ -213,6 +213,7 @@ KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("response", "<f4"), ("le
                            ("gx", "<i4"), ("gy", "<i4")])   # hso_keypoint
 assert KEYPOINT_DTYPE.itemsize == 28
 KP_CORNER_HIGH, KP_EDGELET, KP_GRAD, KP_OCCUR = 0, 1, 2, 3
+E_INVALID, E_UNSUPPORTED, E_TRUNCATED = -1, -5, -6   # HSO_E_* values that appear as per-item results
 ACTIVATE_MAX_TARGETS = 64
 
 
@@ -374,6 +375,8 @@ def load():
     lib.hso_gpu_detect_candidates_multi.argtypes = [vp, P(i64), i32, i32, vp, vp, i32, vp, vp, i32, vp]
     lib.hso_gpu_detect_candidates_init.argtypes = [vp, P(i64), i32, i32, i32, vp, i32, vp, vp, i32, vp]
     lib.hso_gpu_select_octree.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, i32]
+    lib.hso_gpu_select_octree_batch.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp]
+    lib.hso_gpu_detect_select_multi.argtypes = [vp, P(i64), i32, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp]
     lib.hso_gpu_reproject_match_multi.argtypes = [vp, P(Camera), vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, vp, vp]
     lib.hso_gpu_reproject_match.argtypes = [vp, P(Camera), i64, P(SE3), C.c_double, i32, vp, i32, vp, i32, vp, i32, i32, i32,
                                             vp, vp]
@@ -407,6 +410,7 @@ EXPORTED_SYMBOLS = [
     "hso_gpu_seq_chain", "hso_gpu_seq_local_ba", "hso_gpu_seq_events", "hso_gpu_seq_frame_features", "hso_gpu_seq_set_frame_features",
     "hso_gpu_seed_table_observe_groups", "hso_gpu_seed_table_set_host_pose",
     "hso_gpu_seed_table_observe_previous", "hso_gpu_seed_table_observe_previous_begin", "hso_gpu_seed_table_observe_previous_end",
+    "hso_gpu_select_octree_batch", "hso_gpu_detect_select_multi",
 ]
 
 
@@ -987,6 +991,44 @@ class Context:
         self._check(self.lib.hso_gpu_detect_candidates_multi(self.h, ids, n, n_levels, _ptr(th), _ptr(co), corner_cap, _ptr(cc),
                                                              _ptr(eo), edgelet_cap, _ptr(ec)), "detect_candidates_multi")
         return co, cc, eo, ec
+
+    def select_octree_batch(self, key_sets, width, height, n_features, out_cap=None):
+        """hso_gpu_select_octree_batch over (0, width, 0, height): key_sets = KEYPOINT_DTYPE arrays, one per set.  Returns
+        (selections, n_out): selections[i] = the keys written for set i (min(n_out[i], out_cap) of them; none when n_out[i] < 0),
+        n_out[i] = the full count or HSO_E_*.  out_cap defaults to the largest set."""
+        sets = [np.ascontiguousarray(k, KEYPOINT_DTYPE) for k in key_sets]
+        n = len(sets)
+        begin = np.zeros(n + 1, np.int32)
+        begin[1:] = np.cumsum([len(k) for k in sets])
+        keys = np.concatenate(sets) if n else np.zeros(0, KEYPOINT_DTYPE)
+        if out_cap is None:
+            out_cap = max([len(k) for k in sets] + [1])
+        out = np.zeros((max(n, 1), out_cap), KEYPOINT_DTYPE)
+        n_out = np.zeros(max(n, 1), np.int32)
+        self._check(self.lib.hso_gpu_select_octree_batch(self.h, _ptr(keys), _ptr(begin), n, 0, width, 0, height, n_features,
+                                                         _ptr(out), out_cap, _ptr(n_out)), "select_octree_batch")
+        return [out[i, :max(min(int(n_out[i]), out_cap), 0)].copy() for i in range(n)], n_out[:n]
+
+    def detect_select_multi(self, frame_ids, min_thresh, occ_xy, width, height, n_features, n_levels=3, corner_cap=8192, out_cap=None):
+        """hso_gpu_detect_select_multi: occ_xy = one (k_i, 2) float array of occupancy positions per frame.  Returns
+        (selections, n_out, corner_counts[n, L], edgelet_counts[n, L], n_candidates[n]); selections as in select_octree_batch."""
+        n = len(frame_ids)
+        ids = (C.c_int64 * n)(*frame_ids)
+        th = np.ascontiguousarray(min_thresh, np.int32)
+        assert len(th) == n and len(occ_xy) == n
+        occ = [np.ascontiguousarray(o, np.float32).reshape(-1, 2) for o in occ_xy]
+        begin = np.zeros(n + 1, np.int32)
+        begin[1:] = np.cumsum([len(o) for o in occ])
+        xy = np.concatenate(occ) if n else np.zeros((0, 2), np.float32)
+        if out_cap is None:
+            out_cap = max(n_features, 4) + 64
+        out = np.zeros((max(n, 1), out_cap), KEYPOINT_DTYPE)
+        n_out, n_cand = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        cc, ec = np.zeros((n, n_levels), np.int32), np.zeros((n, n_levels), np.int32)
+        self._check(self.lib.hso_gpu_detect_select_multi(self.h, ids, n, n_levels, _ptr(th), corner_cap, _ptr(xy), _ptr(begin),
+                                                         0, width, 0, height, n_features, _ptr(out), out_cap, _ptr(n_out),
+                                                         _ptr(cc), _ptr(ec), _ptr(n_cand)), "detect_select_multi")
+        return [out[i, :max(min(int(n_out[i]), out_cap), 0)].copy() for i in range(n)], n_out[:n], cc, ec, n_cand[:n]
 
     def detect_candidates_init(self, frame_ids, n_levels=3, min_thresh=20, corner_cap=8192, fill_cap=4800):
         """fastDetectMT + fillingHole (the initialisation branch of FeatureExtractor::detect).

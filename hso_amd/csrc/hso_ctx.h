@@ -88,6 +88,8 @@ struct hso_gpu_ctx {
   // hso_lists_to_host: the packed image of many short device lists (device side, page-locked host side), grow-only
   char* d_pack; size_t d_pack_cap;
   char* h_pack; size_t h_pack_cap;
+  // hso_octree_dev.hip: keys, labels, node lists and selections of the oct-tree kernel, grow-only
+  char* d_octree = nullptr; size_t octree_cap = 0;
 };
 
 // Many short device lists (per frame and level: corners, edgelets ...) to caller memory in ONE DMA: a gather kernel packs them back

@@ -357,6 +357,7 @@ void hso_gpu_destroy(hso_gpu_ctx* ctx)
   if (ctx->h_seed_pin) (void)hipHostFree(ctx->h_seed_pin);
   for (int k = 0; k < 2; k++) if (ctx->h_pin[k]) (void)hipHostFree(ctx->h_pin[k]);
   if (ctx->d_pack) (void)hipFree(ctx->d_pack);
+  if (ctx->d_octree) (void)hipFree(ctx->d_octree);
   if (ctx->h_pack) (void)hipHostFree(ctx->h_pack);
   for (void* p : ctx->host_allocs) (void)hipHostFree(p);
   hso_stream_forget(ctx->stream);

@@ -24,6 +24,7 @@
 //   k_edgelet_cells  eight lanes per grid index (one per window row): arg-max of sqrtf(m) over its window
 //   k_edgelet_pack   ordered compaction (grid-index order = the reference's push order)
 #include "hso_fast_plan.h"
+#include "hso_octree_dev.h"
 #include <vector>
 
 #define EDGE_LEVELS HSO_N_SOBEL_LEVELS
@@ -424,16 +425,15 @@ static void canny_thresholds(int min_thresh, int* low, int* high)
   *low = (int)(lo * lo); *high = (int)(hi * hi);
 }
 
+// What a detection leaves in the work area (ctx->d_batch) once its kernels are queued and the closure has ended: the corner lists
+// and totals of the FAST stage (P), the edgelet lists (A.lv[l].o_out of every frame's slice) and totals (A.totals)
+struct DetectRun { FastPlan P; EdgeArgs A; size_t slice; };
+
+// The kernels of a detection, up to the packed lists on the device; n_frames >= 1, arguments checked by the caller.
 // thresh_per_frame != null: every frame has its own minThresh_ (min_thresh is ignored)
-static int detect_candidates_impl(hso_gpu_ctx* ctx, const int64_t* frame_ids, int n_frames, int n_levels, int min_thresh, const int32_t* thresh_per_frame,
-                                  hso_corner* corners, int corner_cap, int32_t* corner_counts,
-                                  hso_edgelet* edgelets, int edgelet_cap, int32_t* edgelet_counts)
+static int detect_candidates_run(hso_gpu_ctx* ctx, const int64_t* frame_ids, int n_frames, int n_levels, int min_thresh, const int32_t* thresh_per_frame,
+                                 int corner_cap, int edgelet_cap, DetectRun* run)
 {
-  if (!ctx) return HSO_E_INVALID;
-  if (!frame_ids || n_frames < 0 || n_levels < 1 || n_levels > EDGE_LEVELS || min_thresh < 0 || min_thresh > 255 || corner_cap < 0 ||
-      edgelet_cap < 0 || !corner_counts || !edgelet_counts || (corner_cap > 0 && !corners) || (edgelet_cap > 0 && !edgelets))
-    return hso_fail(ctx, HSO_E_INVALID, "detect_candidates: bad argument");
-  if (n_frames == 0) return HSO_OK;
   std::vector<int32_t> tab3;   // [FAST threshold | Canny low | Canny high] per frame
   if (thresh_per_frame) {
     tab3.resize(3 * (size_t)n_frames);
@@ -451,7 +451,8 @@ static int detect_candidates_impl(hso_gpu_ctx* ctx, const int64_t* frame_ids, in
   const PyrGeom g = it0->second.g;
   auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
   // extra area: [have flags of every frame | pass flags] (one memset), edgelet totals, then the frame slices
-  EdgeArgs A{};
+  EdgeArgs& A = run->A;
+  A = EdgeArgs{};
   size_t have_bytes = 0, o = 0;
   int vw = g.w[0], vh = g.h[0], max_cells = 0, max_close = 0, max_words = 0, n_tiles = 0;
   for (int l = 0; l < n_levels; l++) {
@@ -490,7 +491,8 @@ static int detect_candidates_impl(hso_gpu_ctx* ctx, const int64_t* frame_ids, in
   const size_t o_slices = o_totals + al(sizeof(int) * (size_t)n_frames * n_levels);
   const size_t extra = o_slices + slice * (size_t)n_frames;
 
-  FastPlan P;
+  FastPlan& P = run->P;
+  run->slice = slice;
   const int rc = hso_fast_enqueue(ctx, frame_ids, n_frames, n_levels, min_thresh, 8, corner_cap, extra, &P,   // fastThresh = floor(minThresh_), border 8 (:520-522)
                                   thresh_per_frame ? tab3.data() : nullptr);
   if (rc != HSO_OK) return rc;
@@ -550,6 +552,23 @@ static int detect_candidates_impl(hso_gpu_ctx* ctx, const int64_t* frame_ids, in
     hipLaunchKernelGGL(k_edgelet_pack, dim3(1, n_levels, n_frames), dim3(PACK_THREADS), 0, ctx->stream, A);
   }
   HSO_HIP_CHECK(ctx, hipGetLastError());
+  return HSO_OK;
+}
+
+static int detect_candidates_impl(hso_gpu_ctx* ctx, const int64_t* frame_ids, int n_frames, int n_levels, int min_thresh, const int32_t* thresh_per_frame,
+                                  hso_corner* corners, int corner_cap, int32_t* corner_counts,
+                                  hso_edgelet* edgelets, int edgelet_cap, int32_t* edgelet_counts)
+{
+  if (!ctx) return HSO_E_INVALID;
+  if (!frame_ids || n_frames < 0 || n_levels < 1 || n_levels > EDGE_LEVELS || min_thresh < 0 || min_thresh > 255 || corner_cap < 0 ||
+      edgelet_cap < 0 || !corner_counts || !edgelet_counts || (corner_cap > 0 && !corners) || (edgelet_cap > 0 && !edgelets))
+    return hso_fail(ctx, HSO_E_INVALID, "detect_candidates: bad argument");
+  if (n_frames == 0) return HSO_OK;
+  DetectRun R;
+  if (int rc = detect_candidates_run(ctx, frame_ids, n_frames, n_levels, min_thresh, thresh_per_frame, corner_cap, edgelet_cap, &R)) return rc;
+  const FastPlan& P = R.P;
+  const EdgeArgs& A = R.A;
+  const size_t slice = R.slice;
   HSO_HIP_CHECK(ctx, hipMemcpyAsync(edgelet_counts, A.totals, sizeof(int) * (size_t)n_frames * n_levels, hipMemcpyDeviceToHost, ctx->stream));
   std::vector<HsoListCopy> lists;
   const int rc2 = hso_fast_collect(ctx, P, corners, corner_counts, &lists);     // synchronises: both count tables are on the host
@@ -577,6 +596,135 @@ extern "C" int hso_gpu_detect_candidates_multi(hso_gpu_ctx* ctx, const int64_t* 
   if (!ctx) return HSO_E_INVALID;
   if (n_frames > 0 && !min_thresh) return hso_fail(ctx, HSO_E_INVALID, "detect_candidates: bad argument");
   return detect_candidates_impl(ctx, frame_ids, n_frames, n_levels, 0, min_thresh, corners, corner_cap, corner_counts, edgelets, edgelet_cap, edgelet_counts);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The keyframe branch fused: the detection above, then allFeturesToDistribute_ assembled on the device from the lists
+// where they lie (the order FeatureExtractor::detect builds it, :408-447: occupancy keys, then per level the corners
+// followed by the edgelets) and the oct-tree kernel (hso_octree_dev.hip) over it.  Only the selected keys and the
+// count tables travel to the host.
+#define KEYTAB_STRIDE (3 + 2 * EDGE_LEVELS)   // per frame: first occupancy pair, first key, ends of the 1 + 2 * n_levels segments
+struct KeyAsmArgs {
+  const char* fast_work; size_t fast_per_frame; size_t o_corner[EDGE_LEVELS];
+  const char* edge_work; size_t edge_per_frame; size_t o_edgelet[EDGE_LEVELS];
+  const float* occ_xy;
+  const int* tab;
+  int n_levels;
+  hso_keypoint* keys;
+};
+
+__global__ __launch_bounds__(256) void k_assemble_keys(KeyAsmArgs A)
+{
+  const int f = blockIdx.y;
+  const int* T = A.tab + (size_t)f * KEYTAB_STRIDE;
+  const int n_seg = 1 + 2 * A.n_levels, n_keys = T[2 + n_seg - 1];
+  for (int j = blockIdx.x * 256 + threadIdx.x; j < n_keys; j += gridDim.x * 256) {
+    int s = 0;
+    while (j >= T[2 + s]) s++;                       // (segments may be empty; j < n_keys = the last end)
+    const int k = j - (s ? T[2 + s - 1] : 0);
+    hso_keypoint kp;
+    kp.response = 0.0f; kp.level = 0; kp.gx = 0; kp.gy = 0;
+    if (s == 0) {
+      const float* xy = A.occ_xy + 2 * ((size_t)T[0] + k);
+      kp.x = xy[0]; kp.y = xy[1]; kp.species = HSO_KP_OCCUR;
+    } else {
+      const int L = (s - 1) >> 1;
+      if ((s - 1) & 1) {
+        const size_t o = L == 0 ? A.o_edgelet[0] : (L == 1 ? A.o_edgelet[1] : A.o_edgelet[2]);
+        const hso_edgelet e = reinterpret_cast<const hso_edgelet*>(A.edge_work + (size_t)f * A.edge_per_frame + o)[k];
+        kp.x = (float)((int)e.x << L); kp.y = (float)((int)e.y << L); kp.response = e.grad; kp.species = HSO_KP_EDGELET; kp.gx = e.gx; kp.gy = e.gy;
+      } else {
+        const size_t o = L == 0 ? A.o_corner[0] : (L == 1 ? A.o_corner[1] : A.o_corner[2]);
+        const hso_corner c = reinterpret_cast<const hso_corner*>(A.fast_work + (size_t)f * A.fast_per_frame + o)[k];
+        kp.x = (float)((int)c.x << L); kp.y = (float)((int)c.y << L); kp.response = c.response; kp.species = HSO_KP_CORNER_HIGH;
+      }
+      kp.level = L;
+    }
+    A.keys[(size_t)T[1] + j] = kp;
+  }
+}
+
+extern "C" int hso_gpu_detect_select_multi(hso_gpu_ctx* ctx, const int64_t* frame_ids, int n_frames, int n_levels, const int32_t* min_thresh, int corner_cap,
+                                           const float* occ_xy, const int32_t* occ_begin,
+                                           int min_x, int max_x, int min_y, int max_y, int n_features,
+                                           hso_keypoint* out, int out_cap, int32_t* n_out,
+                                           int32_t* corner_counts, int32_t* edgelet_counts, int32_t* n_candidates)
+{
+  if (!ctx) return HSO_E_INVALID;
+  if (!frame_ids || n_frames < 0 || n_levels < 1 || n_levels > EDGE_LEVELS || corner_cap < 1 || out_cap < 0 ||
+      (n_frames > 0 && (!min_thresh || !occ_begin || !n_out || !corner_counts || !edgelet_counts || !n_candidates)) || (n_frames > 0 && out_cap > 0 && !out))
+    return hso_fail(ctx, HSO_E_INVALID, "detect_select: bad argument");
+  if (n_frames == 0) return HSO_OK;
+  if (occ_begin[0] != 0) return hso_fail(ctx, HSO_E_INVALID, "detect_select: occ_begin[0] must be 0");
+  for (int i = 0; i < n_frames; i++)
+    if (occ_begin[i + 1] < occ_begin[i]) return hso_fail(ctx, HSO_E_INVALID, "detect_select: occ_begin must not decrease");
+  const size_t n_occ = (size_t)occ_begin[n_frames];
+  if (n_occ > 0 && !occ_xy) return hso_fail(ctx, HSO_E_INVALID, "detect_select: bad argument");
+  OctreePlan plan;
+  if (int rc = hso_octree_plan(ctx, min_x, max_x, min_y, max_y, n_features, &plan)) return rc;
+  auto it0 = ctx->frames.find(frame_ids[0]);
+  if (it0 == ctx->frames.end()) return hso_fail(ctx, HSO_E_NOFRAME, "detect_select: frame not resident");
+  // one edgelet per grid index at most: the level-0 grid's cell count holds every level's list
+  const int edgelet_cap = ((it0->second.g.w[0] + 7) / 8) * ((it0->second.g.h[0] + 7) / 8);
+  DetectRun R;
+  if (int rc = detect_candidates_run(ctx, frame_ids, n_frames, n_levels, 0, min_thresh, corner_cap, edgelet_cap, &R)) return rc;
+  const size_t n_tab = (size_t)n_frames * n_levels;
+  HSO_HIP_CHECK(ctx, hipMemcpyAsync(edgelet_counts, R.A.totals, sizeof(int) * n_tab, hipMemcpyDeviceToHost, ctx->stream));
+  HSO_HIP_CHECK(ctx, hipMemcpyAsync(corner_counts, R.P.d + R.P.o_tot, sizeof(int) * n_tab, hipMemcpyDeviceToHost, ctx->stream));
+  HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  // the key list of every frame; a frame with a truncated list gets none (its n_out says so)
+  std::vector<int32_t> kbeg((size_t)n_frames + 1, 0), tab((size_t)n_frames * KEYTAB_STRIDE, 0);
+  std::vector<char> truncated((size_t)n_frames, 0);
+  size_t total = 0;
+  int most = 0;
+  for (int i = 0; i < n_frames; i++) {
+    int32_t* T = &tab[(size_t)i * KEYTAB_STRIDE];
+    T[0] = occ_begin[i]; T[1] = (int32_t)total;
+    long long at = occ_begin[i + 1] - occ_begin[i];
+    T[2] = (int32_t)at;
+    for (int l = 0; l < n_levels; l++) {
+      const int c = corner_counts[(size_t)i * n_levels + l], e = edgelet_counts[(size_t)i * n_levels + l];
+      if (c > corner_cap || e > edgelet_cap) truncated[(size_t)i] = 1;
+      at += c; T[3 + 2 * l] = (int32_t)at;
+      at += e; T[4 + 2 * l] = (int32_t)at;
+    }
+    n_candidates[i] = (int32_t)at;
+    if (truncated[(size_t)i]) { for (int s = 0; s < 1 + 2 * n_levels; s++) T[2 + s] = 0; at = 0; }
+    if (total + (size_t)at > (size_t)0x7fffffff) return hso_fail(ctx, HSO_E_UNSUPPORTED, "detect_select: more than 2^31 keys in one call");
+    total += (size_t)at;
+    kbeg[(size_t)i + 1] = (int32_t)total;
+    most = at > most ? (int)at : most;
+  }
+  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+  const size_t o_kbeg = 0, o_tab = al(sizeof(int) * kbeg.size()), o_nout = o_tab + al(sizeof(int) * tab.size());
+  const size_t o_occ = o_nout + al(sizeof(int) * (size_t)n_frames), o_keys = o_occ + al(sizeof(float) * 2 * n_occ);
+  const size_t o_out = o_keys + al(sizeof(hso_keypoint) * total), o_scratch = o_out + al(sizeof(hso_keypoint) * (size_t)n_frames * out_cap);
+  char* d = nullptr;
+  if (int rc = hso_octree_reserve(ctx, o_scratch + hso_octree_scratch_bytes(plan, n_frames, total), &d)) return rc;
+  HSO_HIP_CHECK(ctx, hipMemcpyAsync(d + o_kbeg, kbeg.data(), sizeof(int) * kbeg.size(), hipMemcpyHostToDevice, ctx->stream));
+  HSO_HIP_CHECK(ctx, hipMemcpyAsync(d + o_tab, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, ctx->stream));
+  if (n_occ > 0) HSO_HIP_CHECK(ctx, hipMemcpyAsync(d + o_occ, occ_xy, sizeof(float) * 2 * n_occ, hipMemcpyHostToDevice, ctx->stream));
+  if (most > 0) {
+    KeyAsmArgs K;
+    K.fast_work = R.P.d; K.fast_per_frame = R.P.per_frame;
+    K.edge_work = R.A.work; K.edge_per_frame = R.slice;
+    for (int l = 0; l < EDGE_LEVELS; l++) { K.o_corner[l] = l < n_levels ? R.P.o_out[l] : 0; K.o_edgelet[l] = l < n_levels ? R.A.lv[l].o_out : 0; }
+    K.occ_xy = reinterpret_cast<const float*>(d + o_occ);
+    K.tab = reinterpret_cast<const int*>(d + o_tab);
+    K.n_levels = n_levels;
+    K.keys = reinterpret_cast<hso_keypoint*>(d + o_keys);
+    hipLaunchKernelGGL(k_assemble_keys, dim3((most + 255) / 256, n_frames), dim3(256), 0, ctx->stream, K);
+    HSO_HIP_CHECK(ctx, hipGetLastError());
+  }
+  if (int rc = hso_octree_launch(ctx, plan, reinterpret_cast<const hso_keypoint*>(d + o_keys), reinterpret_cast<const int*>(d + o_kbeg), n_frames, total,
+                                 reinterpret_cast<hso_keypoint*>(d + o_out), out_cap, reinterpret_cast<int*>(d + o_nout), d + o_scratch))
+    return rc;
+  HSO_HIP_CHECK(ctx, hipMemcpyAsync(n_out, d + o_nout, sizeof(int) * (size_t)n_frames, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_cap > 0)
+    HSO_HIP_CHECK(ctx, hipMemcpyAsync(out, d + o_out, sizeof(hso_keypoint) * (size_t)n_frames * out_cap, hipMemcpyDeviceToHost, ctx->stream));
+  HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  for (int i = 0; i < n_frames; i++) if (truncated[(size_t)i]) n_out[i] = HSO_E_TRUNCATED;
+  return HSO_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

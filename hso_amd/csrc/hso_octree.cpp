@@ -2,8 +2,8 @@
 // FeatureExtractor::detect (reference src/feature_detection.cpp:449-455 calling
 // computeKeyPointsOctTree :833-1122, ExtractorNode::DivideNode include/hso/feature_detection.h:217-272).
 //
-// Host code behind the C-ABI (no GPU work: a few thousand candidates, a sequential refinement whose
-// every step depends on the previous one).  The reference keeps a std::list of nodes that each own
+// Host code behind the C-ABI, and the definition of the selection: the device version (hso_octree_dev.hip, one
+// workgroup per keyframe) is held to this function's output byte for byte.  The reference keeps a std::list of nodes that each own
 // a std::vector of KeyPoints and copies the keys on every split.  Here the candidates are never
 // copied: one index array is partitioned in place (stably, so a child sees its keys in the parent's
 // order — the order the reference's push_back produces), a node is {rectangle, index range, links}

@@ -182,7 +182,7 @@ Bank::~Bank()
     delete s;
   }
   for (StepData* d : step_) delete d;
-  chain_res_.release(); chain_brief_.release(); feat_rows_.release(); track_tables_.release(); act_seeds_.release(); act_targets_.release(); act_ints_.release(); act_slots_.release(); act_out_.release(); seed_brief_.release(); seed_px_.release(); det_corners_.release(); det_fill_.release(); det_edgelets_.release();   // before the context goes
+  chain_res_.release(); chain_brief_.release(); feat_rows_.release(); track_tables_.release(); act_seeds_.release(); act_targets_.release(); act_ints_.release(); act_slots_.release(); act_out_.release(); seed_brief_.release(); seed_px_.release(); det_corners_.release(); det_fill_.release(); det_edgelets_.release(); det_sel_.release(); det_occ_.release();   // before the context goes
   if (owns_ctx_) hso_gpu_destroy(ctx_);
 }
 
@@ -225,11 +225,12 @@ void Bank::pin_threads()
   pinned_driver_ = me; driver_pinned_ = true;
 }
 
-void Bank::set_options(bool sync_previous, bool track_no_coop, bool no_numa_pin)
+void Bank::set_options(bool sync_previous, bool track_no_coop, bool no_numa_pin, bool device_select)
 {
   previous_collect();                                            // a pass in flight is applied under the old setting
   sync_previous_ = sync_previous;
   no_numa_pin_ = no_numa_pin;
+  device_select_ = device_select;
   hso_gpu_options o{};
   o.size = (int32_t)sizeof(o); o.track_no_coop = track_no_coop ? 1 : 0;
   check(hso_gpu_configure(ctx_, &o), "configure");

@@ -181,7 +181,7 @@ public:
   int trajectory(int k, double* stamps, hso_se3* T_f_w, int cap) const;
   bool trace(int k, const char* path);
   bool trace_state(int k, bool on);
-  void set_options(bool sync_previous, bool track_no_coop, bool no_numa_pin = false);
+  void set_options(bool sync_previous, bool track_no_coop, bool no_numa_pin = false, bool device_select = false);
   void call_counts(int64_t* calls, int64_t* items, int cap) const;
   // algorithmic bytes (SURVEY.md section 8(d) units) of the steps so far: [frame build, tracker, matcher, pose optimiser, seeds]
   void alg_bytes(double* out, int cap) const { for (int i = 0; i < cap && i < 5; i++) out[i] = alg_bytes_[i]; }
@@ -231,6 +231,8 @@ private:
   void release_frame_deferred(Seq& s, StepData& d, Id fr);
   void detect(const std::vector<int>& who, const std::vector<Id>& frame, const std::vector<int>& thresh, bool init, int n_levels, int n_features,
               std::vector<std::vector<hso_keypoint>>& keys, std::vector<std::vector<hso_keypoint>>& sel);
+  bool detect_select_device(const std::vector<int>& who, const std::vector<Id>& frame, const std::vector<int>& thresh, int n_levels, int n_features,
+                            const std::vector<std::vector<hso_keypoint>>& keys, std::vector<std::vector<hso_keypoint>>& sel);
   Feat feature_from_key(const hso_keypoint& kp, Id fr) const;
 
   hso_gpu_ctx* ctx_;
@@ -287,6 +289,9 @@ private:
   Pinned<float> seed_px_;
   Pinned<hso_corner> det_corners_, det_fill_;   // detect(): the candidate lists of a step's new keyframes
   Pinned<hso_edgelet> det_edgelets_;
+  Pinned<hso_keypoint> det_sel_;                // ... and, with device_select_, the selected keys instead
+  Pinned<float> det_occ_;
+  bool device_select_ = false;                  // hso_vo_options.device_select
   int det_corner_cap_ = 8192;                   // corners per (frame, level) the lists hold; grows when a frame has more
 };
 

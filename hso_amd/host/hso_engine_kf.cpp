@@ -3,6 +3,13 @@
 #include "hso_engine_impl.h"
 #include <optional>
 
+// Referenced weakly: the engine also links against a CPU stand-in of the device library (tests/fakegpu) that has no such entry;
+// there the address is null and Bank::detect stays on the host path.
+extern "C" int hso_gpu_detect_select_multi(hso_gpu_ctx* ctx, const int64_t* frame_ids, int n_frames, int n_levels, const int32_t* min_thresh, int corner_cap,
+                                           const float* occ_xy, const int32_t* occ_begin, int min_x, int max_x, int min_y, int max_y, int n_features,
+                                           hso_keypoint* out, int out_cap, int32_t* n_out, int32_t* corner_counts, int32_t* edgelet_counts,
+                                           int32_t* n_candidates) __attribute__((weak));
+
 namespace hso {
 namespace engine {
 
@@ -578,13 +585,60 @@ void Bank::previous_collect()
   erase_slots(who);
 }
 
+// The keyframe branch of Bank::detect with hso_vo_options.device_select: detection, key assembly and the oct-tree in one device call
+// (hso_gpu_detect_select_multi); keys[i] holds the occupancy keys on entry and is left as it is (nothing reads the full candidate
+// list but the trace, and a traced step takes the host path).  false: the host path has to do it (no such entry in the device
+// library, a key the entry would not build itself, or a request beyond the kernel's limits).
+bool Bank::detect_select_device(const std::vector<int>& who, const std::vector<Id>& frame, const std::vector<int>& thresh, int n_levels, int n_features,
+                                const std::vector<std::vector<hso_keypoint>>& keys, std::vector<std::vector<hso_keypoint>>& sel)
+{
+  if (!hso_gpu_detect_select_multi || who.empty()) return false;
+  const int n = (int)who.size(), W = cam_.width(), H = cam_.height();
+  std::vector<int64_t> ids((size_t)n);
+  std::vector<int32_t> ths((size_t)n), ob((size_t)n + 1, 0);
+  for (int i = 0; i < n; i++) {
+    if (seq_[who[i]]->trace.on()) return false;
+    for (const hso_keypoint& k : keys[i])
+      if (k.species != HSO_KP_OCCUR || k.response != 0.f || k.level != 0 || k.gx != 0 || k.gy != 0) return false;
+    ids[(size_t)i] = seq_[who[i]]->frames[frame[i]].dev_id; ths[(size_t)i] = thresh[i];
+    ob[(size_t)i + 1] = ob[(size_t)i] + (int32_t)keys[i].size();
+  }
+  float* occ = det_occ_.need(ctx_, 2 * (size_t)std::max(ob[(size_t)n], 1));
+  for (int i = 0; i < n; i++)
+    for (size_t j = 0; j < keys[i].size(); j++) { occ[2 * ((size_t)ob[(size_t)i] + j)] = keys[i][j].x; occ[2 * ((size_t)ob[(size_t)i] + j) + 1] = keys[i][j].y; }
+  // the node list ends within 3 of n_features, or at the first sweep's 4 nodes per initial column
+  const int out_cap = std::max(n_features, 0) + 3 + 4 * (W / H + 2);
+  hso_keypoint* out = det_sel_.need(ctx_, (size_t)n * out_cap);
+  std::vector<int32_t> n_out((size_t)n), nc((size_t)n * n_levels), ne((size_t)n * n_levels), n_cand((size_t)n);
+  for (;;) {
+    const int rc = hso_gpu_detect_select_multi(ctx_, ids.data(), n, n_levels, ths.data(), det_corner_cap_, occ, ob.data(), 0, W, 0, H, n_features,
+                                               out, out_cap, n_out.data(), nc.data(), ne.data(), n_cand.data());
+    if (rc == HSO_E_UNSUPPORTED) return false;
+    check(rc, "FeatureExtractor");
+    n_calls_[9]++; n_items_[9] += n;
+    const int most = *std::max_element(nc.begin(), nc.end());
+    if (most <= det_corner_cap_) break;
+    det_corner_cap_ = most + most / 4;                            // more corners than the lists hold: once more with room for all
+  }
+  for (int i = 0; i < n; i++)
+    if (n_out[(size_t)i] == HSO_E_UNSUPPORTED || n_out[(size_t)i] == HSO_E_TRUNCATED || n_out[(size_t)i] > out_cap) return false;
+  for (int i = 0; i < n; i++) {
+    if (n_out[(size_t)i] < 0) throw std::runtime_error("FeatureExtractor: oct-tree selection failed");
+    sel[(size_t)i].assign(out + (size_t)i * out_cap, out + (size_t)i * out_cap + n_out[(size_t)i]);
+  }
+  return true;
+}
+
 // FeatureExtractor::detect (src/feature_detection.cpp:408-497) for one new keyframe per sequence: candidates on the device (batched
-// per detection threshold), the oct-tree distribution on the host; sel[i] receives the selected keys of who[i]
+// per detection threshold), the oct-tree distribution on the host — or, for new keyframes with hso_vo_options.device_select, both on
+// the device; sel[i] receives the selected keys of who[i]
 void Bank::detect(const std::vector<int>& who, const std::vector<Id>& frame, const std::vector<int>& thresh, bool init, int n_levels, int n_features,
                   std::vector<std::vector<hso_keypoint>>& keys, std::vector<std::vector<hso_keypoint>>& sel)
 {
   const int W = cam_.width(), H = cam_.height();
   const int second_cap = ((W + 7) / 8) * ((H + 7) / 8);
+  sel.assign(who.size(), {});
+  if (!init && device_select_ && detect_select_device(who, frame, thresh, n_levels, n_features, keys, sel)) return;
   sel.assign(who.size(), {});
   std::vector<int> todo(who.size());
   std::iota(todo.begin(), todo.end(), 0);

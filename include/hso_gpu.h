@@ -41,7 +41,8 @@ enum {
   HSO_E_NOFRAME = -2,   /* frame id not resident in the context */
   HSO_E_HIP = -3,       /* HIP runtime error, see hso_gpu_last_error */
   HSO_E_NOMEM = -4,
-  HSO_E_UNSUPPORTED = -5
+  HSO_E_UNSUPPORTED = -5,
+  HSO_E_TRUNCATED = -6  /* per-item result of hso_gpu_detect_select_multi: a candidate list held more entries than its capacity */
 };
 
 /* ---- camera: AbstractCamera {Pinhole, FOV, Equidistant}, src/camera.cpp ---- */
@@ -1071,7 +1072,7 @@ int hso_gpu_detect_candidates_init(hso_gpu_ctx* ctx, const int64_t* frame_ids, i
 
 /* ---- FeatureExtractor::computeKeyPointsOctTree, src/feature_detection.cpp:833-1122 (ExtractorNode::DivideNode,
  *      include/hso/feature_detection.h:217-272): the spatial distribution that ends FeatureExtractor::detect
- *      (:449-455).  Host code (sequential refinement over a few thousand candidates), no context needed. ---- */
+ *      (:449-455).  Host code, no context needed: the definition the device version below is held to. ---- */
 enum { HSO_KP_CORNER_HIGH = 0, HSO_KP_EDGELET = 1, HSO_KP_GRAD = 2, HSO_KP_OCCUR = 3 };  /* FeatureSpecies, feature_detection.h:180-186 */
 typedef struct hso_keypoint {   /* KeyPoint, include/hso/feature_detection.h:188-208 */
   float x, y;          /* level-0 pixels */
@@ -1090,6 +1091,41 @@ typedef struct hso_keypoint {   /* KeyPoint, include/hso/feature_detection.h:188
  * (std::sort over (size, pointer) pairs, :974), node creation order is used. */
 int hso_gpu_select_octree(const hso_keypoint* keys, int n, int min_x, int max_x, int min_y, int max_y, int n_features,
                              hso_keypoint* out, int cap);
+
+/* ---- the same distribution on the device (src/feature_detection.cpp:833-1122; hso_amd/csrc/hso_octree_dev.hip): one workgroup
+ *      per key set, every set's selection byte for byte what hso_gpu_select_octree returns for it — the same keys, in the
+ *      same order (the node list from its head), the same count.  hso_gpu_select_octree stays the definition.
+ *      Value-passing: the keys of n_sets sets go up in one copy (set i = keys[key_begin[i] .. key_begin[i + 1]), key_begin[0]
+ *      = 0), one launch, the selections come back in one copy: set i at out + i * out_cap.  n_out[i] = what the host function
+ *      returns for set i: the full count (at most out_cap keys written), or HSO_E_INVALID for a set with a key whose column
+ *      falls outside the rectangle; the other sets are unaffected by such a set.  The call itself returns HSO_OK unless an
+ *      argument is bad.
+ *      Limits: n_features <= 4096 and round(width / height) of the rectangle <= 64 (HSO_E_UNSUPPORTED beyond; both are
+ *      call-wide); any number of keys per set (labels and node lists live in device memory, not in LDS; the keyframe branch
+ *      has < 16384, n_features = Config::maxFts() + 100, the initialisation 2000).  Positions and responses are finite
+ *      (the host function's comparisons are undefined for NaN as well); -0.0 and +0.0 responses tie, as on the host. ---- */
+int hso_gpu_select_octree_batch(hso_gpu_ctx* ctx, const hso_keypoint* keys, const int32_t* key_begin, int n_sets,
+                                int min_x, int max_x, int min_y, int max_y, int n_features,
+                                hso_keypoint* out, int out_cap, int32_t* n_out);
+
+/* ---- FeatureExtractor::detect's keyframe branch in one call (src/feature_detection.cpp:408-455 with
+ *      computeKeyPointsOctTree :833-1122): the detection of hso_gpu_detect_candidates_multi (frame_ids, n_frames, n_levels,
+ *      min_thresh[n_frames], corner_cap as there; the edgelet capacity is the level-0 grid's cell count and cannot
+ *      overflow), then allFeturesToDistribute_ assembled on the device from the lists where they lie, then the oct-tree
+ *      kernel above.  Frame i's keys, in order: its occupancy positions occ_xy[2 * occ_begin[i] .. 2 * occ_begin[i + 1])
+ *      (x, y pairs; species HSO_KP_OCCUR, every other field 0: setExistingFeatures :1169-1177), then per level L the
+ *      corners (position (x << L, y << L), response = hso_corner.response, species HSO_KP_CORNER_HIGH, gx = gy = 0)
+ *      followed by the edgelets (response = hso_edgelet.grad, species HSO_KP_EDGELET, gx, gy the edgelet's).
+ *      Only the selected keys (frame i at out + i * out_cap) and the count tables come back: n_out[n_frames] as in
+ *      hso_gpu_select_octree_batch, corner_counts / edgelet_counts [n_frames * n_levels] the full list lengths,
+ *      n_candidates[n_frames] the length of the frame's key list (occupancy keys included).  A frame with a level that holds
+ *      more corners than corner_cap is not selected from: its n_out is HSO_E_TRUNCATED and corner_counts tells the caller
+ *      how much room a repeat needs; the other frames are unaffected.  Limits as for hso_gpu_select_octree_batch. ---- */
+int hso_gpu_detect_select_multi(hso_gpu_ctx* ctx, const int64_t* frame_ids, int n_frames, int n_levels, const int32_t* min_thresh, int corner_cap,
+                                const float* occ_xy, const int32_t* occ_begin,
+                                int min_x, int max_x, int min_y, int max_y, int n_features,
+                                hso_keypoint* out, int out_cap, int32_t* n_out,
+                                int32_t* corner_counts, int32_t* edgelet_counts, int32_t* n_candidates);
 
 /* ---- two-view initialisation, image side: initialization::trackKlt (src/initialization.cpp:225-300) =
  *      cv::calcOpticalFlowPyrLK(img_prev, img_cur, px_prev, px_cur, status, error, Size(30, 30), 4,

@@ -45,7 +45,11 @@ typedef struct hso_vo_options {
   int32_t no_numa_pin;        /* 0 (default): from a handle's next step on, the thread that drives it and its worker threads run on the CPUs of the NUMA node
                                  the device is attached to (hso_gpu_device_cpulist, intersected with the affinity the process has) — page-locked
                                  staging and the runtime's queues stay node-local; 1: affinities are left alone (set before the first frame) */
-  int32_t reserved[4];
+  int32_t device_select;      /* 1: a new keyframe's features are selected on the device (hso_gpu_detect_select_multi: detection, key assembly and the
+                                 oct-tree in one call, only the selected keys come back) instead of on the worker pool; same results: tests compare.
+                                 The initialisation, a step in which a sequence records a trace, and a device library without the entry
+                                 keep the host path */
+  int32_t reserved[3];
 } hso_vo_options;
 int hso_vo_set_options(hso_vo* vo, const hso_vo_options* options);
 /* first keyframe: features are detected the way the initialisation detects them and every feature with
