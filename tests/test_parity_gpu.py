@@ -10,7 +10,11 @@ Bar:
                (CoarseTracker.cpp:272; tens of thousands of fp32 adds) and 2e-6 against
                the fp64 sum of the same fp32 terms;
                pose: rotation <= 1e-6 rad, translation <= 1e-6 * scene depth (4 m);
-               frame means: 2e-5 relative (reference: serial fp32 sums over 3e5 pixels).
+               frame means: 2e-5 relative against the oracle's serial fp32 sums over 3e5 pixels — on the
+               noise-plus-ramp and rendered images only, whose gradient mean is far above the clamp
+               (both sides return 20.0: the assert covers the intensity mean and the clamp, nothing
+               else); on the unclamped texture images: integral_image bit-equal and grad_mean 1e-6
+               relative against frame_ref.stats_exact (exact integers, math.fsum), not the oracle.
 """
 import json
 import os
@@ -19,6 +23,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from frame_ref import stats_exact, texture
 from hso_amd import capi, synth
 
 pytestmark = pytest.mark.gpu
@@ -67,6 +72,49 @@ def test_frame_pyramid_sobel_stats(gpu_ctx, orc, spec):
     assert st.grad_mean == pytest.approx(so.grad_mean, rel=2e-5)
     assert (st.width, st.height) == (w, h)
     gpu_ctx.frame_release(900)
+    # a second image whose gradient mean is NOT clamped (the one above: about 41, both sides return 20.0), against exact arithmetic
+    tex = texture(w, h, 16, 1000 * w + h)
+    ex = stats_exact(tex)
+    assert 7.5 < ex.unclamped < 19.5
+    st2 = gpu_ctx.frame_upload(900, tex)
+    try:
+        _assert_stats_exact(st2, ex)
+        _assert_stats_exact(gpu_ctx.debug_frame_stats(900), ex)
+        # No rel=2e-5 device-versus-oracle assert here: the oracle repeats the reference's serial fp32 sum over 2.8e5 / 3.2e5
+        # terms and is itself 8.0e-5 (640x480) / 7.0e-5 (752x480) away from the exact gradient mean of this image, 1.4e-5 /
+        # 1.3e-5 from the exact intensity mean (_oracle_distance below computes both); a perfect kernel would fail it.
+        d_grad, d_int = _oracle_distance(orc, tex, ex)
+        assert 2e-5 < d_grad < 1e-3 and d_int < 1e-3
+    finally:
+        gpu_ctx.frame_release(900)
+
+
+def _release_if_resident(ctx, frame_id):
+    try:
+        ctx.frame_release(frame_id)
+    except capi.HsoGpuError:
+        pass
+
+
+def _assert_stats_exact(st, ex):
+    """device statistics of an unclamped image against frame_ref.stats_exact: the intensity mean bit for bit (exact integer sum,
+    one fp64 division, one rounding on both sides), the gradient mean to 1e-6 (test_frame_geometry_gpu.py derives < 4e-7)"""
+    assert 7.5 < ex.unclamped < 19.5
+    assert np.float32(st.integral_image).tobytes() == ex.integral_image.tobytes(), (st.integral_image, ex.integral_image)
+    dev = abs(st.grad_mean - float(ex.grad_mean)) / float(ex.grad_mean)
+    print("grad_mean deviation %dx%d: %.3e" % (ex.width, ex.height, dev))
+    assert dev <= 1e-6, (st.grad_mean, float(ex.grad_mean), dev)
+    assert (st.width, st.height) == (ex.width, ex.height)
+
+
+def _oracle_distance(orc, img, ex):
+    """relative distance of the oracle's (serial fp32) statistics to the exact ones: (gradient mean, intensity mean).  A random
+    walk of n = 3e5 .. 7e5 roundings of 2^-24 each predicts some 1e-5 .. 1e-4; the worst case n * 2^-24 is 0.02 .. 0.04."""
+    so = orc.frame_stats(img, *orc.sobel5(img))
+    d_grad = abs(so.grad_mean - float(ex.grad_mean)) / float(ex.grad_mean)
+    d_int = abs(so.integral_image - float(ex.integral_image)) / float(ex.integral_image)
+    print("oracle-to-exact distance %dx%d: grad_mean %.3e, integral_image %.3e" % (ex.width, ex.height, d_grad, d_int))
+    return d_grad, d_int
 
 
 def test_frame_batch_equals_single_and_device_source(gpu_ctx, orc):
@@ -490,8 +538,24 @@ def test_resize_branch_frame_and_tracker(gpu_ctx, orc):
         # the reference sums 6.2e5 pixels serially in fp32 (frame.cpp:223-236): its own rounding
         # error grows with the pixel count; the device sum is an exact integer
         assert st_c.integral_image == pytest.approx(so.integral_image, rel=1e-4)
-        assert st_c.integral_image == pytest.approx(float(cp[0][16:-16, 16:-16].astype(np.float64).mean()), rel=1e-6)
+        ex_c = stats_exact(d["cur"])
+        assert np.float32(st_c.integral_image).tobytes() == ex_c.integral_image.tobytes()
         assert st_c.grad_mean == pytest.approx(so.grad_mean, rel=1e-4)
+        assert ex_c.unclamped > 20 and st_c.grad_mean == 20.0       # the rendered image is clamped (about 50): 20.0 against 20.0
+        # an image whose gradient mean is not clamped, against exact arithmetic (the oracle's serial sum is 6.4e-5 away from it
+        # on this image, 1.7e-5 on the intensity mean: no device-versus-oracle assert)
+        tex = texture(w, h, 16, 1000 * w + h)
+        ex = stats_exact(tex)
+        assert 7.5 < ex.unclamped < 19.5
+        _release_if_resident(gpu_ctx, 912)
+        st_t = gpu_ctx.frame_upload(912, tex)
+        try:
+            _assert_stats_exact(st_t, ex)
+            _assert_stats_exact(gpu_ctx.debug_frame_stats(912), ex)
+            d_grad, d_int = _oracle_distance(orc, tex, ex)
+            assert 2e-5 < d_grad < 1e-3 and d_int < 1e-3
+        finally:
+            gpu_ctx.frame_release(912)
         # tracker: per-level evaluation parity and the full run
         p = capi.TrackParams(0, 4, 1, 50)
         job = gpu_ctx.make_job(910, 911, d["feats"], capi.SE3.identity(), 1.0)
