@@ -324,6 +324,7 @@ def load():
     lib.hso_gpu_frame_download_sobel.argtypes = [vp, i64, i32, vp, vp]
     lib.hso_gpu_debug_sobel_taps.argtypes = [vp, i64, i32, vp, vp]
     lib.hso_gpu_debug_frame_stats.argtypes = [vp, i64, P(FrameStats)]
+    lib.hso_gpu_debug_wave_primitives.argtypes = [vp, vp, i32, vp, i32]
     lib.hso_gpu_make_depth_ref.argtypes = [vp, vp, i32, vp, i32, P(SE3), vp]
     lib.hso_gpu_coarse_track_batch.argtypes = [vp, P(Camera), P(TrackParams), P(TrackJob), i32, P(TrackResult)]
     lib.hso_gpu_coarse_track_prepare.argtypes = [vp, P(Camera), P(TrackParams), P(TrackJob), i32]
@@ -416,7 +417,8 @@ EXPORTED_SYMBOLS = [
 
 # ... and every symbol include/hso_gpu_debug.h declares (parity / trace read-backs, developer probes: not part of the boundary)
 DEBUG_SYMBOLS = ["hso_gpu_debug_census", "hso_gpu_klt_debug_level", "hso_gpu_seq_debug_list", "hso_gpu_seq_debug_ref_table", "hso_gpu_debug_fetch",
-                 "hso_gpu_seqmap_debug_dump", "hso_gpu_seq_ba_debug_window", "hso_gpu_debug_sobel_taps", "hso_gpu_debug_frame_stats"]
+                 "hso_gpu_seqmap_debug_dump", "hso_gpu_seq_ba_debug_window", "hso_gpu_debug_sobel_taps", "hso_gpu_debug_frame_stats",
+                 "hso_gpu_debug_wave_primitives"]
 
 
 def select_octree(keys, width, height, n_features):
@@ -603,6 +605,13 @@ class Context:
         gy = np.empty_like(gx)
         self._check(self.lib.hso_gpu_debug_sobel_taps(self.h, frame_id, level, _ptr(gx), _ptr(gy)), "debug_sobel_taps")
         return gx, gy
+
+    def debug_wave_primitives(self, values):
+        """hso_gpu_debug_wave_primitives: values float64 [128, 32] -> float64 [128, 32] (the fields of include/hso_gpu_debug.h)"""
+        values = np.ascontiguousarray(values, np.float64)
+        out = np.empty((128, 32), np.float64)
+        self._check(self.lib.hso_gpu_debug_wave_primitives(self.h, _ptr(values), values.size, _ptr(out), out.size), "debug_wave_primitives")
+        return out
 
     # -- tracker
     def make_depth_ref(self, din, poses, T_ref_w):

@@ -143,15 +143,10 @@ __global__ __launch_bounds__(256) void k_activate_finish(ActConsts C, const ActS
 // residual and Jacobian; the sums the reference forms in a serial loop over the targets are formed
 // in the same order by walking the lanes 0..n-1 with a broadcast each (unmatched lanes contribute
 // an exact 0.0), so H, b and the energies carry the reference's rounding.
-HSO_DEV double act_bcast(double v, int src)
-{
-  const int lo = __shfl(__double2loint(v), src), hi = __shfl(__double2hiint(v), src);
-  return __hiloint2double(hi, lo);
-}
 HSO_DEV double act_ordered_sum(double x, int n)
 {
   double s = 0;
-  for (int i = 0; i < n; i++) s += act_bcast(x, i);
+  for (int i = 0; i < n; i++) s += wave_shfl(x, i);
   return s;
 }
 
@@ -290,7 +285,7 @@ __global__ __launch_bounds__(64 * ACT_OPT_WAVES) void k_activate_opt(ActConsts C
         }
       }
       double Hh = 0, b = 0;
-      for (int i = 0; i < n; i++) { Hh += act_bcast(h_i, i); b -= act_bcast(b_i, i); }  // H += ..., b -= ... (:951-967)
+      for (int i = 0; i < n; i++) { Hh += wave_shfl(h_i, i); b -= wave_shfl(b_i, i); }  // H += ..., b -= ... (:951-967)
       Hh *= 1.0 + mu;
       const double step = b / Hh;
       if (!isnan(step)) {

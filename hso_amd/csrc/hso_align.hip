@@ -558,9 +558,7 @@ static __global__ void k_scatter_links(int32_t* __restrict__ dst, const int32_t*
 template <int W> __device__ int sel_scan_waves(int v, int* s_wave, int& total)
 {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if (lane >= d) incl += o; }
+  const int incl = wave_inclusive_scan(v, lane);
   __syncthreads();
   if (lane == 63) s_wave[wave] = incl;
   __syncthreads();
@@ -573,9 +571,7 @@ template <int W> __device__ int sel_scan_waves(int v, int* s_wave, int& total)
 __device__ int sel_scan256(int v, int* s_wave, int& total)
 {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if (lane >= d) incl += o; }
+  const int incl = wave_inclusive_scan(v, lane);
   __syncthreads();
   if (lane == 63) s_wave[wave] = incl;
   __syncthreads();

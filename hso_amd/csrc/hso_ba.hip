@@ -441,10 +441,7 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_poses(const BaProb* probs, co
   for (int q = 0; q < 44; q++) {
     double x = acc[q];
 #pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-      const int lo = __shfl_xor(__double2loint(x), m), hi = __shfl_xor(__double2hiint(x), m);
-      x += __hiloint2double(hi, lo);
-    }
+    for (int m = 32; m >= 1; m >>= 1) x += wave_shfl_xor(x, m);
     if (lane == 0) s_part[wave][q] = x;
   }
   __syncthreads();
@@ -494,7 +491,7 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_maxdiag(const BaProb* probs, 
     if (!P.a.fixed[i]) m = fmax(m, fabs(P.Hcc[((size_t)i * np + i) * 36 + q * 7]));
   }
 #pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) m = fmax(m, __hiloint2double(__shfl_xor(__double2hiint(m), d), __shfl_xor(__double2loint(m), d)));
+  for (int d = 32; d >= 1; d >>= 1) m = fmax(m, wave_shfl_xor(m, d));
   if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = m;
   __syncthreads();
   if (threadIdx.x == 0) { double t = 0; for (int w = 0; w < BA_WAVES; w++) t = fmax(t, s_part[w]); P.sum[5] = t; }
@@ -601,8 +598,8 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_chi2(const BaProb* probs, BaL
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) {
-    c += __hiloint2double(__shfl_xor(__double2hiint(c), m), __shfl_xor(__double2loint(c), m));
-    r += __hiloint2double(__shfl_xor(__double2hiint(r), m), __shfl_xor(__double2loint(r), m));
+    c += wave_shfl_xor(c, m);
+    r += wave_shfl_xor(r, m);
   }
   if (lane == 0) { s_part[wave][0] = c; s_part[wave][1] = r; }
   __syncthreads();
@@ -1534,9 +1531,7 @@ struct RbaWinDev {
 template <int W> __device__ inline int rba_scan(int v, int* s_wave, int& total)
 {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(x, d); if (lane >= d) x += y; }
+  const int x = wave_inclusive_scan(v, lane);
   if (lane == 63) s_wave[wave] = x;
   __syncthreads();
   int base = 0, tot = 0;

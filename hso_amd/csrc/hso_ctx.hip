@@ -2,6 +2,7 @@
 #include <algorithm>
 #define HSO_RAW_HIP_COPIES          // this file implements the copy wrappers: it alone calls the runtime's copy functions
 #include "hso_ctx.h"
+#include "hso_wave.h"
 #include <string.h>
 #include <atomic>
 #include <chrono>
@@ -466,6 +467,71 @@ int hso_lists_to_host(hso_gpu_ctx* ctx, const std::vector<HsoListCopy>& lists)
   HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   at = 0;
   for (size_t i = 0; i < n; i++) { memcpy(live[i]->dst, ctx->h_pack + tab + at, live[i]->bytes); at += live[i]->bytes; }
+  return HSO_OK;
+}
+
+// ---- hso_gpu_debug_wave_primitives (include/hso_gpu_debug.h): every primitive of hso_wave.h by itself, two wavefronts
+__global__ __launch_bounds__(HSO_WAVE_DBG_THREADS) void k_debug_wave(const double* in, double* out)
+{
+  using namespace hso_dev;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double v[HSO_WAVE_DBG_VALUES], v8[8];
+  float f[HSO_WAVE_DBG_VALUES];
+#pragma unroll
+  for (int i = 0; i < HSO_WAVE_DBG_VALUES; i++) { v[i] = in[threadIdx.x * HSO_WAVE_DBG_VALUES + i]; f[i] = (float)v[i]; }
+#pragma unroll
+  for (int i = 0; i < 8; i++) v8[i] = v[i];
+  double* o = out + threadIdx.x * HSO_WAVE_DBG_FIELDS;
+  o[HSO_WAVE_BUTTERFLY_F64] = wave_butterfly_sum(v[0]);
+  o[HSO_WAVE_BUTTERFLY_F32] = wave_butterfly_sum(f[1]);
+  o[HSO_WAVE_BUTTERFLY_I32] = wave_butterfly_sum((int)v[2]);
+  o[HSO_WAVE_TO_LANE63_F64] = wave_sum_to_lane63(v[3]);
+  o[HSO_WAVE_TO_LANE63_I32] = wave_sum_to_lane63((int)v[4]);
+  o[HSO_WAVE_XOR_F64 + 0] = lane_xor<32>(v[5]); o[HSO_WAVE_XOR_F64 + 1] = lane_xor<16>(v[5]); o[HSO_WAVE_XOR_F64 + 2] = lane_xor<8>(v[5]);
+  o[HSO_WAVE_XOR_F64 + 3] = lane_xor<4>(v[5]); o[HSO_WAVE_XOR_F64 + 4] = lane_xor<2>(v[5]); o[HSO_WAVE_XOR_F64 + 5] = lane_xor<1>(v[5]);
+  o[HSO_WAVE_XOR_F32 + 0] = lane_xor<32>(f[6]); o[HSO_WAVE_XOR_F32 + 1] = lane_xor<16>(f[6]); o[HSO_WAVE_XOR_F32 + 2] = lane_xor<8>(f[6]);
+  o[HSO_WAVE_XOR_F32 + 3] = lane_xor<4>(f[6]); o[HSO_WAVE_XOR_F32 + 4] = lane_xor<2>(f[6]); o[HSO_WAVE_XOR_F32 + 5] = lane_xor<1>(f[6]);
+  o[HSO_WAVE_SCAN_I32] = wave_inclusive_scan((int)v[7], lane);
+  int slot;
+  double td;
+  float tf;
+  wave_halve<double, 32, 32>(v, lane, slot, td);
+  o[HSO_WAVE_HALVE32_F64] = slot; o[HSO_WAVE_HALVE32_F64 + 1] = td;
+  wave_halve<float, 32, 32>(f, lane, slot, tf);
+  o[HSO_WAVE_HALVE32_F32] = slot; o[HSO_WAVE_HALVE32_F32 + 1] = tf;
+  wave_halve<double, 8, 32>(v8, lane, slot, td);
+  o[HSO_WAVE_HALVE8_F64] = slot; o[HSO_WAVE_HALVE8_F64 + 1] = td;
+  o[HSO_WAVE_ROW16_F32] = row_sum16(f[8]);
+  o[HSO_WAVE_ROW8_F32] = row_sum8(f[9]);
+  o[HSO_WAVE_SWAP32_F64] = lane_swap_sum<32>(v[10], v[11]);
+  o[HSO_WAVE_SWAP16_F32] = lane_swap_sum<16>(f[10], f[11]);
+  o[HSO_WAVE_SHFL_F64] = wave_shfl(v[12], (5 * lane + 3) & 63);
+  o[HSO_WAVE_SHFL_XOR_F64] = wave_shfl_xor(v[12], 21 << wave);
+  o[HSO_WAVE_SHFL_XOR_I64] = (double)wave_shfl_xor((long long)v[12], 21 << wave);
+  o[HSO_WAVE_DBG_FIELDS - 1] = 0;
+}
+
+extern "C" int hso_gpu_debug_wave_primitives(hso_gpu_ctx* ctx, const double* in, int n_in, double* out, int n_out)
+{
+  if (!ctx || !in || !out) return HSO_E_INVALID;
+  if (n_in != HSO_WAVE_DBG_THREADS * HSO_WAVE_DBG_VALUES || n_out != HSO_WAVE_DBG_THREADS * HSO_WAVE_DBG_FIELDS)
+    return hso_fail(ctx, HSO_E_INVALID, "debug_wave_primitives: n_in / n_out are not the sizes the header states");
+  const size_t b_in = (size_t)n_in * sizeof(double), b_out = (size_t)n_out * sizeof(double), need = b_in + b_out;
+  HSO_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (ctx->batch_cap < need) {
+    HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->d_batch) (void)hipFree(ctx->d_batch);
+    ctx->d_batch = nullptr; ctx->batch_cap = 0;
+    HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_batch), hso_grown(need)));
+    ctx->batch_cap = hso_grown(need);
+  }
+  double* d_in = reinterpret_cast<double*>(ctx->d_batch);
+  double* d_out = reinterpret_cast<double*>(ctx->d_batch + b_in);
+  HSO_HIP_CHECK(ctx, hipMemcpyAsync(d_in, in, b_in, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(k_debug_wave, dim3(1), dim3(HSO_WAVE_DBG_THREADS), 0, ctx->stream, d_in, d_out);
+  HSO_HIP_CHECK(ctx, hipGetLastError());
+  HSO_HIP_CHECK(ctx, hipMemcpyAsync(out, d_out, b_out, hipMemcpyDeviceToHost, ctx->stream));
+  HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return HSO_OK;
 }
 

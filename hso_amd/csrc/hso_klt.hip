@@ -15,6 +15,7 @@
 // sequence (until the median disparity reaches Config::initMinDisparity); it is here so that the product path starts from two
 // images without leaving the device interface, not because it is hot.
 #include "hso_ctx.h"
+#include "hso_wave.h"
 
 namespace {
 
@@ -69,10 +70,7 @@ struct KltLevels {
 
 __device__ __forceinline__ long long wave_sum_i64(long long v)
 {
-  for (int o = 32; o > 0; o >>= 1) {
-    const int lo = __shfl_xor((int)(v & 0xffffffffll), o), hi = __shfl_xor((int)(v >> 32), o);
-    v += ((long long)hi << 32) | (unsigned)lo;
-  }
+  for (int o = 32; o > 0; o >>= 1) v += hso_dev::wave_shfl_xor(v, o);
   return v;
 }
 

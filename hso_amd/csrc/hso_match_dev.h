@@ -54,14 +54,7 @@ HSO_DEV unsigned load_px_pair(const uint8_t* p) { return *(const __attribute__((
 
 // ---- sixteen lanes per patch: a DPP row owns an 8x8 patch, a lane four horizontally adjacent pixels of it (pixel (px0 + j, py),
 // j = 0..3, of lane l16 = lane & 15: py = l16 >> 1, px0 = (l16 & 1) * 4).  Four patches per wavefront, sums inside the row.
-HSO_DEV float row_sum_all(float v)
-{
-  v += __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), 0x128, 0xf, 0xf, false));   // row_ror:8
-  v += __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), 0x124, 0xf, 0xf, false));   // row_ror:4
-  v += __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), 0x4e, 0xf, 0xf, false));    // quad_perm:[2,3,0,1]
-  v += __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), 0xb1, 0xf, 0xf, false));    // quad_perm:[1,0,3,2]
-  return v;   // every lane of the row holds the same bits (each step adds the same two partial sums in both partners)
-}
+HSO_DEV float row_sum_all(float v) { return row_sum16(v); }   // hso_wave.h: every lane of the row holds the same bits
 HSO_DEV float row_sum4(const float (&v)[4]) { return row_sum_all((v[0] + v[1]) + (v[2] + v[3])); }
 
 // the 5 + 5 bytes a lane's four bilinear samples need: two unaligned 8-byte loads (the rows are followed by at least one

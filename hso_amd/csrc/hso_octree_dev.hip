@@ -19,6 +19,7 @@
 // second phase's sort keys are in LDS, which is what bounds n_features (HSO_OCTREE_MAX_FEATURES).  Counters that
 // atomics update are read and written with agent-scope atomic accesses only, so no plain load can meet a stale L1 line.
 #include "hso_octree_dev.h"
+#include "hso_wave.h"
 #include <cmath>
 
 #define OCT_THREADS 1024
@@ -41,9 +42,7 @@ __device__ __forceinline__ void oct_st(int* p, int v) { __hip_atomic_store(p, v,
 __device__ __forceinline__ int oct_scan(int v, int* s_w, int& total)
 {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(inc, d); if (lane >= d) inc += o; }
+  const int inc = hso_dev::wave_inclusive_scan(v, lane);
   if (lane == 63) s_w[wv] = inc;
   __syncthreads();
   int before = 0, tot = 0;

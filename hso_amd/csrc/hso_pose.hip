@@ -16,7 +16,7 @@
 // MAD scales and medians are exact order statistics (bitwise search on the IEEE bit patterns).
 #include "hso_pose_dev.h"
 #include "hso_dev_math.h"
-#include "hso_wave_reduce.h"
+#include "hso_wave.h"
 #include <string.h>
 #include <algorithm>
 #include <vector>
@@ -60,9 +60,10 @@ HSO_DEV void pose_block_sum27_1(PoseShared& s, double (&v)[32], double c, double
 {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int slot;
-  const double x = wave_reduce_scatter32(v, lane, slot);
+  double x;
+  wave_halve<double, 32, 32>(v, lane, slot, x);
   const double cw = wave_butterfly_sum(c);
-  if ((lane & 1) == 0 && slot < 27) s.wave_part[wave][slot] = x;
+  if (wave_halve_first<32, 32>(lane) && slot < 27) s.wave_part[wave][slot] = x;
   if (lane == 0) s.wave_part[wave][27] = cw;
   __syncthreads();
   if (threadIdx.x < 28) {
@@ -96,8 +97,7 @@ HSO_DEV void pose_pick_bin(PoseShared& s, int which, int half, unsigned rank)
   unsigned c = 0, incl = 0;
   if (mine) {
     c = s.hist[which][bin];
-    incl = c;
-    for (int d = 1; d < 64; d <<= 1) { const unsigned o = __shfl_up(incl, d); if (lane >= d) incl += o; }
+    incl = wave_inclusive_scan(c, lane);
     if (lane == 63) s.cnt[wave] = (int)incl;
   }
   __syncthreads();

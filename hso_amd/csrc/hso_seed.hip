@@ -65,13 +65,7 @@ struct SeedDev {
 //     (~17 wave-instructions per seed and step);
 //   * the KLT iterations depend on one another, so there the eight lanes share an iteration (eight pixels each, a patch sum is
 //     seven adds and three DPP steps inside the group) and the uniform arithmetic of an iteration serves eight seeds.
-HSO_DEV float grp_sum_all(float v)
-{
-  v += __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), 0x141, 0xf, 0xf, false));   // row_half_mirror: l8 <-> 7 - l8
-  v += __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), 0xb1, 0xf, 0xf, false));    // quad_perm:[1,0,3,2]
-  v += __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), 0x4e, 0xf, 0xf, false));    // quad_perm:[2,3,0,1]
-  return v;   // the same bits in all eight lanes: every step adds the same two partial sums in both partners
-}
+HSO_DEV float grp_sum_all(float v) { return row_sum8(v); }   // hso_wave.h: the same bits in all eight lanes
 HSO_DEV float grp_sum8(const float (&v)[8]) { return grp_sum_all(((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]))); }
 // the value lane `j` of the caller's group of eight holds
 HSO_DEV float grp_get(float v, int j) { return __uint_as_float((unsigned)__builtin_amdgcn_ds_bpermute((int)((((threadIdx.x & 63) & ~7) | j) << 2), (int)__float_as_uint(v))); }

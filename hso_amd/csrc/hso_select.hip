@@ -55,9 +55,7 @@ struct SelArgs {
 template <int W> __device__ int sel_block_scan_w(int v, int* s_wave, int& total)
 {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if (lane >= d) incl += o; }
+  const int incl = wave_inclusive_scan(v, lane);
   __syncthreads();
   if (lane == 63) s_wave[wave] = incl;
   __syncthreads();

@@ -33,6 +33,7 @@
 #include "hso_ctx.h"
 #include <stdlib.h>
 #include "hso_dev_math.h"
+#include "hso_wave.h"   // at file scope: hso_tracker_core.h is included inside namespaces
 #include <string.h>
 #include <algorithm>
 #include <condition_variable>

@@ -22,6 +22,7 @@
 #include "hso_ctx.h"
 #include <stdlib.h>
 #include "hso_dev_math.h"
+#include "hso_wave.h"   // at file scope: hso_tracker_core.h is included inside a namespace
 #include <string.h>
 #include <algorithm>
 

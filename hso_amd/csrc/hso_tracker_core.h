@@ -72,17 +72,6 @@ HSO_DEV float b1f(uint32_t v) { return (float)((v >> 8) & 0xffu); }
 HSO_DEV float b2f(uint32_t v) { return (float)((v >> 16) & 0xffu); }
 HSO_DEV float b3f(uint32_t v) { return (float)(v >> 24); }
 
-HSO_DEV double shfl_d(double v, int src)
-{
-  const int lo = __shfl(__double2loint(v), src), hi = __shfl(__double2hiint(v), src);
-  return __hiloint2double(hi, lo);
-}
-HSO_DEV double shfl_xor_d(double v, int m)
-{
-  const int lo = __shfl_xor(__double2loint(v), m), hi = __shfl_xor(__double2hiint(v), m);
-  return __hiloint2double(hi, lo);
-}
-
 // FOV (atan) camera: rare, transcendental-heavy — kept out of line so that it does not
 // inflate the register budget of the hot loops
 __device__ __noinline__ void world2cam_fov(const hso_camera* cam, double x, double y, double z, double* pu, double* pv)
@@ -195,104 +184,8 @@ struct Acc {
                  // (integers far below 2^24: exact in fp32); [30..31] pad
   double d[8];   // b[0..6] (fp64 like CoarseTracker.cpp:520), E — eight values: the halving exchange needs no pad
                  // (with the two counts as doubles it carried 6 zero values = 12 of its 32 dword exchanges)
-};               // sizes padded to powers of two for the halving exchange (the pads stay 0)
-
-// Sum N (a power of two <= 64) per-lane values over the 64 lanes of a wave by recursive
-// halving: at each step (lane distance 32, 16, ...) a lane hands the half of its values it
-// is not responsible for to its partner and adds the partner's contribution to the half it
-// keeps, so N values cost ~N exchanges instead of 6N.  Afterwards the lane whose `slot` is
-// k (< N) holds the total of value k.  Fixed order => deterministic floating point.
-// Lane exchanges of the halving sum, cheapest form per distance (gfx950):
-//   32, 16  v_permlane32_swap / v_permlane16_swap: the instruction swaps the upper half (odd rows) of one register with the
-//           lower half (even rows) of another — exactly "hand over the half you do not keep": afterwards both registers
-//           hold, in every lane, the two values that lane has to add.  No select, no LDS crossbar trip;
-//   8, 2, 1 DPP (row_ror:8, quad_perm) on the value handed over;
-//   4       two DPP moves (quad_perm [3,2,1,0], then row_half_mirror).
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-template <int M> HSO_DEV unsigned xor_lane_u32(unsigned v)
-{
-  if constexpr (M == 8) return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xf, 0xf, false);       // row_ror:8
-  else if constexpr (M == 2) return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4e, 0xf, 0xf, false);  // quad_perm:[2,3,0,1]
-  else if constexpr (M == 1) return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xb1, 0xf, 0xf, false);  // quad_perm:[1,0,3,2]
-  else return lane_xor_u32<M>(v);   // 4: two DPP moves (hso_dev_math.h)
-}
-template <int M> HSO_DEV float xor_lane(float v) { return __uint_as_float(xor_lane_u32<M>(__float_as_uint(v))); }
-template <int M> HSO_DEV double xor_lane(double v)
-{
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  const unsigned lo = xor_lane_u32<M>((unsigned)b), hi = xor_lane_u32<M>((unsigned)(b >> 32));
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-// lanes with (lane & M) == 0 get lo + lo', the others hi + hi' (primes: the partner lane's values)
-template <int M> HSO_DEV float swap_sum(float lo, float hi)
-{
-  static_assert(M == 32 || M == 16, "swap distances");
-  u32x2 r;
-  if constexpr (M == 32) r = __builtin_amdgcn_permlane32_swap(__float_as_uint(lo), __float_as_uint(hi), false, false);
-  else r = __builtin_amdgcn_permlane16_swap(__float_as_uint(lo), __float_as_uint(hi), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-template <int M> HSO_DEV double swap_sum(double lo, double hi)
-{
-  const unsigned long long bl = (unsigned long long)__double_as_longlong(lo), bh = (unsigned long long)__double_as_longlong(hi);
-  u32x2 r0, r1;
-  if constexpr (M == 32) {
-    r0 = __builtin_amdgcn_permlane32_swap((unsigned)bl, (unsigned)bh, false, false);
-    r1 = __builtin_amdgcn_permlane32_swap((unsigned)(bl >> 32), (unsigned)(bh >> 32), false, false);
-  } else {
-    r0 = __builtin_amdgcn_permlane16_swap((unsigned)bl, (unsigned)bh, false, false);
-    r1 = __builtin_amdgcn_permlane16_swap((unsigned)(bl >> 32), (unsigned)(bh >> 32), false, false);
-  }
-  const double a = __longlong_as_double((long long)(((unsigned long long)r1[0] << 32) | r0[0]));
-  const double b = __longlong_as_double((long long)(((unsigned long long)r1[1] << 32) | r0[1]));
-  return a + b;
-}
-
-template <typename T, int N, int M>
-struct Halve {
-  static HSO_DEV void run(T (&v)[N], int lane, int& slot, T& out)
-  {
-    static_assert((N & (N - 1)) == 0 && N >= 2, "N must be a power of two");
-    constexpr int HALF = N / 2;
-    const bool up = (lane & M) != 0;
-    T keep[HALF];
-#pragma unroll
-    for (int i = 0; i < HALF; i++) {
-      const T lo = v[i];
-      const T hi = v[HALF + i];
-      if constexpr (M == 32 || M == 16) {
-        keep[i] = swap_sum<M>(lo, hi);
-      } else {
-        const T send = up ? lo : hi;
-        keep[i] = (up ? hi : lo) + xor_lane<M>(send);
-      }
-    }
-    if (up) slot += HALF;
-    if constexpr (M == 1) {
-      out = keep[0];  // HALF == 1 here
-    } else {
-      Halve<T, HALF, M / 2>::run(keep, lane, slot, out);
-    }
-  }
-};
-template <typename T, int M> HSO_DEV void butterfly_from(T& x)
-{
-  if constexpr (M == 32 || M == 16) x = swap_sum<M>(x, x);
-  else x += xor_lane<M>(x);
-  if constexpr (M > 1) butterfly_from<T, M / 2>(x);
-}
-template <typename T, int M>
-struct Halve<T, 1, M> {
-  static HSO_DEV void run(T (&v)[1], int lane, int& slot, T& out)
-  {
-    // a single value left before the lane distance reached 1: finish with plain butterflies
-    T x = v[0];
-    butterfly_from<T, M>(x);
-    // every lane of the remaining group holds the total; only the group's first lane reports it
-    if ((lane & (2 * M - 1)) != 0) slot = 1 << 20;
-    out = x;
-  }
-};
+};               // sizes padded to powers of two for the halving exchange (hso_wave.h: wave_halve; the pads stay 0)
+constexpr int TRK_NO_SLOT = 1 << 20;   // the slot of a lane that stores no total
 
 HSO_DEV int block_sum_int(Shared& s, int v)
 {
@@ -571,9 +464,6 @@ HSO_DEV void precompute_reference(const Shared& s, const LevelCtx& L, Ptr ref32)
 
 // ------------------------------------------------------ robust thresholds
 
-#ifndef TRK_ROW_WINDOWS
-#define TRK_ROW_WINDOWS 1
-#endif
 #ifndef TRK_PRECOMPUTE_ROWS
 #define TRK_PRECOMPUTE_ROWS 1   // pattern-specialised reference patch precompute (forward mode, reference level in LDS)
 #endif
@@ -836,21 +726,13 @@ HSO_DEV void scan_find(const unsigned* hist, unsigned& rank, unsigned& bin, unsi
   asm volatile("" : "+v"(lane));
   unsigned local = 0;
   for (int j = 0; j < SEG; j++) local += hist[lane * SEG + ((j + lane) & (SEG - 1))];  // rotated start: spreads the banks
-  unsigned incl = local;
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned o = __shfl_up(incl, d);
-    if (lane >= d) incl += o;
-  }
+  const unsigned incl = wave_inclusive_scan(local, lane);
   const unsigned excl = incl - local;
   const unsigned long long m = __ballot(rank >= excl && rank < incl);
   const int seg = (m != 0ull) ? (__ffsll((long long)m) - 1) : 0;
   const unsigned r2 = rank - __shfl(excl, seg);
   const unsigned c = (lane < SEG) ? hist[seg * SEG + lane] : 0u;
-  unsigned incl2 = c;
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned o = __shfl_up(incl2, d);
-    if (lane >= d) incl2 += o;
-  }
+  const unsigned incl2 = wave_inclusive_scan(c, lane);
   const unsigned long long m2 = __ballot(lane < SEG && r2 >= incl2 - c && r2 < incl2);
   const int bl = (m2 != 0ull) ? (__ffsll((long long)m2) - 1) : 0;
   bin = (unsigned)(seg * SEG + bl);
@@ -1012,9 +894,7 @@ struct MemKeys {
 #pragma unroll
       for (int i = 0; i < NK; i++) mbits |= (unsigned long long)((k[i] >> SEL_A_SHIFT) == bin ? 1u : 0u) << i;
       const int c = (int)__popcll(mbits);
-      int incl = c;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if (lane >= d) incl += o; }
+      const int incl = wave_inclusive_scan(c, lane);
       const int total = __shfl(incl, 63);
       if (total == 0) continue;
       int base = 0;
@@ -1192,58 +1072,6 @@ HSO_DEV Moments feature_terms(const Shared& s, const LevelCtx& L, Ptr img, const
     // saturated terms contribute no Jacobian row (:350-355): weight 0
     const float w = sat ? 0.0f : hw;
     const float e = -t.iref;
-    const float we = w * e, wx = w * dx, wy = w * dy, wr = w * res;
-    m.ee = fmaf(we, e, m.ee); m.ex = fmaf(we, dx, m.ex); m.ey = fmaf(we, dy, m.ey);
-    m.xx = fmaf(wx, dx, m.xx); m.xy = fmaf(wx, dy, m.xy); m.yy = fmaf(wy, dy, m.yy);
-    m.re = fmaf(wr, e, m.re); m.rx = fmaf(wr, dx, m.rx); m.ry = fmaf(wr, dy, m.ry);
-  }
-  return m;
-}
-
-// The same arithmetic (forward mode, image in LDS) with the pattern known at compile time
-// (PI = index into the static pattern tables), fully unrolled: tap offsets oy*stride+ox and
-// patch-cache offsets k*n_max are scalar expressions, there is no per-term table read and no
-// loop-carried prefetch record — about a quarter fewer instructions per term in a loop that is
-// VALU-issue-bound.  Deliberately NOT inlined: inside the megakernel the unrolled body competes
-// with the state of every other phase for the 168 VGPRs and spills; as a separate function it gets
-// its own register allocation, at the price of one call per feature.
-template <int PI>
-__device__ __forceinline__ Moments feature_terms_static(LdsPtr img, GlbF32 ref_patch, int base, float w_tl, float w_tr, float w_bl,
-                                                      float w_br, uint32_t fb, uint32_t nb, int stride, float a, float huber,
-                                                      float outlier, float max_energy, int top)
-{
-  constexpr int PA = h_pattern_num[PI];
-  Moments m;
-  m.ee = m.ex = m.ey = m.xx = m.xy = m.yy = m.re = m.rx = m.ry = 0; m.E = 0; m.nt = PA; m.nsat = 0;
-  stride = __builtin_amdgcn_readfirstlane(stride);
-  nb = (uint32_t)__builtin_amdgcn_readfirstlane((int)nb);
-  typedef const __attribute__((address_space(1))) char* GlbBytes;
-  const GlbBytes rpb = (GlbBytes)ref_patch;
-  constexpr int PF = 4;  // reference intensities requested PF terms ahead of their use
-  float ipf[PF];
-#pragma unroll
-  for (int k = 0; k < PF && k < PA; k++) ipf[k] = *(GlbF32)(rpb + (fb + (uint32_t)k * nb));
-#pragma unroll
-  for (int k = 0; k < PA; k++) {
-    const int ox = h_pattern[PI][k][0], oy = h_pattern[PI][k][1];
-    const int a0 = base + (oy * stride + ox);
-    const uint32_t r1 = fetch4(img, a0), r2 = fetch4(img, a0 + stride);
-    const uint32_t r0 = fetch4(img, a0 - stride), r3 = fetch4(img, a0 + 2 * stride);
-    const float iref = ipf[k % PF];
-    if (k + PF < PA) ipf[k % PF] = *(GlbF32)(rpb + (fb + (uint32_t)(k + PF) * nb));
-    const float p11 = b1f(r1), p12 = b2f(r1), p21 = b1f(r2), p22 = b2f(r2);
-    const float cur = ((w_tl * p11 + w_tr * p12) + w_bl * p21) + w_br * p22;
-    const float res = cur - a * iref;
-    const float ares = fabsf(res);
-    const float hw = ares < huber ? 1.0f : huber * __builtin_amdgcn_rcpf(ares);
-    const bool sat = (ares > outlier) && !top;
-    const float e_term = top ? (hw * res) * res : ((hw * res) * res) * (2 - hw);
-    m.E += sat ? max_energy : e_term;
-    m.nsat += sat ? 1 : 0;
-    const float dx = fmaf(w_tl, p12 - b0f(r1), fmaf(w_tr, b3f(r1) - p11, fmaf(w_bl, p22 - b0f(r2), w_br * (b3f(r2) - p21))));
-    const float dy = fmaf(w_tl, p21 - b1f(r0), fmaf(w_tr, p22 - b2f(r0), fmaf(w_bl, b1f(r3) - p11, w_br * (b2f(r3) - p12))));
-    const float w = sat ? 0.0f : hw;
-    const float e = -iref;
     const float we = w * e, wx = w * dx, wy = w * dy, wr = w * res;
     m.ee = fmaf(we, e, m.ee); m.ex = fmaf(we, dx, m.ex); m.ey = fmaf(we, dy, m.ey);
     m.xx = fmaf(wx, dx, m.xx); m.xy = fmaf(wx, dy, m.xy); m.yy = fmaf(wy, dy, m.yy);
@@ -1555,13 +1383,8 @@ HSO_PHASE void eval_terms(Shared& s, const LevelCtx& L, Ptr img, const Se3& T, f
           m[q] = Moments{};
       } else if constexpr (PI >= 0) {
         if (p[q].ok)
-#if TRK_ROW_WINDOWS
           m[q] = feature_terms_rows<PI>(img, (GlbF32)L.sc.ref_patch, p[q].base, p[q].w_tl, p[q].w_tr, p[q].w_bl, p[q].w_br,
                                         (uint32_t)f * 4u, (uint32_t)L.C->n_max * 4u, L.cols, a, huber, outlier, max_energy, top ? 1 : 0);
-#else
-          m[q] = feature_terms_static<PI>(img, (GlbF32)L.sc.ref_patch, p[q].base, p[q].w_tl, p[q].w_tr, p[q].w_bl, p[q].w_br,
-                                          (uint32_t)f * 4u, (uint32_t)L.C->n_max * 4u, L.cols, a, huber, outlier, max_energy, top ? 1 : 0);
-#endif
         else
           m[q] = Moments{};
       } else {
@@ -1588,9 +1411,11 @@ HSO_PHASE void eval_terms(Shared& s, const LevelCtx& L, Ptr img, const Se3& T, f
       if (p[q].ok && sub == 0) expand_feature<IC>(acc, L, p[q], m[q], ff[q], a);
     DBG_T(2);
     float th; double td;
-    slotH = 0; slotD = 0;
-    Halve<float, 32, 32>::run(acc.H, lane, slotH, th);
-    Halve<double, 8, 32>::run(acc.d, lane, slotD, td);
+    // every lane of a slot holds its total (hso_wave.h: wave_halve); only the slot's first lane reports it
+    wave_halve<float, 32, 32>(acc.H, lane, slotH, th);
+    if (!wave_halve_first<32, 32>(lane)) slotH = TRK_NO_SLOT;
+    wave_halve<double, 8, 32>(acc.d, lane, slotD, td);
+    if (!wave_halve_first<8, 32>(lane)) slotD = TRK_NO_SLOT;
     totH += th;
     totD += td;
     DBG_T(3);

@@ -78,6 +78,29 @@ int hso_gpu_debug_sobel_taps(hso_gpu_ctx* ctx, int64_t frame, int level, int16_t
 /* test hook: the statistics record a resident frame carries on the device now (what its upload returned, unless something wrote it since) */
 int hso_gpu_debug_frame_stats(hso_gpu_ctx* ctx, int64_t frame, hso_frame_stats* out);
 
+/* test hook: the wave64 lane-exchange primitives of the device code (hso_amd/csrc/hso_wave.h), each by itself.  One workgroup of
+ * HSO_WAVE_DBG_THREADS threads (two wavefronts); thread t reads in[t * HSO_WAVE_DBG_VALUES + i] (small integers, so that every sum
+ * is exact in fp32 and fp64) and writes out[t * HSO_WAVE_DBG_FIELDS + field].  With lane = t % 64, wave = t / 64, v[i] thread t's
+ * inputs (converted to the field's type):
+ *   BUTTERFLY_F64 / _F32 / _I32   wave_butterfly_sum(v[0] / v[1] / v[2])
+ *   TO_LANE63_F64 / _I32          wave_sum_to_lane63(v[3] / v[4]): defined in lane 63 only
+ *   XOR_F64 + k, XOR_F32 + k      lane_xor<32 >> k>(v[5] / v[6]), k = 0..5
+ *   SCAN_I32                      wave_inclusive_scan(v[7])
+ *   HALVE32_F64 / HALVE32_F32     wave_halve<T, 32, 32> of v[0..32): slot, then the total the lane holds
+ *   HALVE8_F64                    wave_halve<double, 8, 32> of v[0..8): slot, total
+ *   ROW16_F32 / ROW8_F32          row_sum16(v[8]) / row_sum8(v[9])
+ *   SWAP32_F64 / SWAP16_F32       lane_swap_sum<32>(v[10], v[11]) / lane_swap_sum<16>(v[10], v[11])
+ *   SHFL_F64                      wave_shfl(v[12], (5 * lane + 3) % 64)
+ *   SHFL_XOR_F64 / _I64           wave_shfl_xor(v[12], 21 << wave), double / long long
+ * n_in must be HSO_WAVE_DBG_THREADS * HSO_WAVE_DBG_VALUES, n_out HSO_WAVE_DBG_THREADS * HSO_WAVE_DBG_FIELDS. */
+#define HSO_WAVE_DBG_THREADS 128
+#define HSO_WAVE_DBG_VALUES 32
+enum { HSO_WAVE_BUTTERFLY_F64 = 0, HSO_WAVE_BUTTERFLY_F32 = 1, HSO_WAVE_BUTTERFLY_I32 = 2, HSO_WAVE_TO_LANE63_F64 = 3, HSO_WAVE_TO_LANE63_I32 = 4,
+       HSO_WAVE_XOR_F64 = 5, HSO_WAVE_XOR_F32 = 11, HSO_WAVE_SCAN_I32 = 17, HSO_WAVE_HALVE32_F64 = 18, HSO_WAVE_HALVE32_F32 = 20,
+       HSO_WAVE_HALVE8_F64 = 22, HSO_WAVE_ROW16_F32 = 24, HSO_WAVE_ROW8_F32 = 25, HSO_WAVE_SWAP32_F64 = 26, HSO_WAVE_SWAP16_F32 = 27,
+       HSO_WAVE_SHFL_F64 = 28, HSO_WAVE_SHFL_XOR_F64 = 29, HSO_WAVE_SHFL_XOR_I64 = 30, HSO_WAVE_DBG_FIELDS = 32 };
+int hso_gpu_debug_wave_primitives(hso_gpu_ctx* ctx, const double* in, int n_in, double* out, int n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -698,6 +698,34 @@ int hso_gpu_seqmap_debug_dump(hso_gpu_ctx* c, int m, int what, void* out, size_t
 
 void hso_gpu_debug_census(int64_t* out, int n) { for (int i = 0; i < n; i++) out[i] = 0; }   // no runtime underneath
 
+// what the contracts of hso_amd/csrc/hso_wave.h say every lane holds, by plain loops over the 64 lanes of the thread's wavefront
+// (the inputs are small integers: every sum is exact, whatever its order)
+int hso_gpu_debug_wave_primitives(hso_gpu_ctx* c, const double* in, int n_in, double* out, int n_out)
+{
+  const int T = HSO_WAVE_DBG_THREADS, V = HSO_WAVE_DBG_VALUES, F = HSO_WAVE_DBG_FIELDS;
+  if (!in || !out || n_in != T * V || n_out != T * F) return fail(c, HSO_E_INVALID, "debug_wave_primitives: sizes");
+  for (int t = 0; t < T; t++) {
+    const int lane = t & 63, wave = t >> 6, first = t & ~63;
+    auto val = [&](int l, int i) { return in[(first + l) * V + i]; };
+    auto sum = [&](int i, int l0, int n) { double s = 0; for (int l = l0; l < l0 + n; l++) s += val(l, i); return s; };
+    double* o = out + t * F;
+    for (int k = 0; k < F; k++) o[k] = 0;
+    o[HSO_WAVE_BUTTERFLY_F64] = sum(0, 0, 64); o[HSO_WAVE_BUTTERFLY_F32] = sum(1, 0, 64); o[HSO_WAVE_BUTTERFLY_I32] = sum(2, 0, 64);
+    if (lane == 63) { o[HSO_WAVE_TO_LANE63_F64] = sum(3, 0, 64); o[HSO_WAVE_TO_LANE63_I32] = sum(4, 0, 64); }
+    for (int k = 0; k < 6; k++) { o[HSO_WAVE_XOR_F64 + k] = val(lane ^ (32 >> k), 5); o[HSO_WAVE_XOR_F32 + k] = val(lane ^ (32 >> k), 6); }
+    o[HSO_WAVE_SCAN_I32] = sum(7, 0, lane + 1);
+    o[HSO_WAVE_HALVE32_F64] = o[HSO_WAVE_HALVE32_F32] = lane / 2;
+    o[HSO_WAVE_HALVE32_F64 + 1] = o[HSO_WAVE_HALVE32_F32 + 1] = sum(lane / 2, 0, 64);
+    o[HSO_WAVE_HALVE8_F64] = lane / 8; o[HSO_WAVE_HALVE8_F64 + 1] = sum(lane / 8, 0, 64);
+    o[HSO_WAVE_ROW16_F32] = sum(8, lane & ~15, 16); o[HSO_WAVE_ROW8_F32] = sum(9, lane & ~7, 8);
+    o[HSO_WAVE_SWAP32_F64] = val(lane, (lane & 32) ? 11 : 10) + val(lane ^ 32, (lane & 32) ? 11 : 10);
+    o[HSO_WAVE_SWAP16_F32] = val(lane, (lane & 16) ? 11 : 10) + val(lane ^ 16, (lane & 16) ? 11 : 10);
+    o[HSO_WAVE_SHFL_F64] = val((5 * lane + 3) & 63, 12);
+    o[HSO_WAVE_SHFL_XOR_F64] = o[HSO_WAVE_SHFL_XOR_I64] = val(lane ^ (21 << wave), 12);
+  }
+  return HSO_OK;
+}
+
 int hso_gpu_debug_fetch(hso_gpu_ctx* c, int what, void* out, size_t bytes)
 {
   const void* src = nullptr; size_t have = 0;

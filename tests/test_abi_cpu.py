@@ -39,6 +39,21 @@ def test_library_exports_every_declared_symbol(lib):
     assert not [n for n in names if "debug" in n]
 
 
+def test_wave_primitives_restatement():
+    """tests/fakegpu's host restatement of hso_gpu_debug_wave_primitives meets the expectations the device library is held to
+    (tests/test_wave_gpu.py), and refuses sizes other than the header's"""
+    import subprocess
+    import wave_ref
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "fakegpu")])
+    fake = C.CDLL(os.path.join(ROOT, "tests", "fakegpu", "libhso_host_fake.so"))
+    fake.hso_gpu_debug_wave_primitives.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    values = wave_ref.inputs()
+    out = np.full((wave_ref.THREADS, wave_ref.FIELDS), np.nan)
+    assert fake.hso_gpu_debug_wave_primitives(None, values.ctypes.data, values.size, out.ctypes.data, out.size) == 0
+    wave_ref.check(values, out)
+    assert fake.hso_gpu_debug_wave_primitives(None, values.ctypes.data, values.size - 1, out.ctypes.data, out.size) < 0
+
+
 def test_abi_version_and_struct_layout(lib):
     assert lib.hso_gpu_abi_version() == capi.ABI_VERSION == 2
     # POD layouts the header promises (checked against the C compiler's view by the sizes the
