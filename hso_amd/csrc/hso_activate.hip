@@ -324,16 +324,15 @@ __global__ __launch_bounds__(64 * ACT_OPT_WAVES) void k_activate_opt(ActConsts C
 struct ActLayout { size_t o_seeds, o_pin, o_frames, o_pout, o_jobs, o_match, o_out, need; };
 static ActLayout act_layout(int n_seeds, int n_pairs, int n_frames)
 {
-  auto al = [](size_t v) { return (v + 255) & ~size_t(255); };
   ActLayout L;
   L.o_seeds = 0;
-  L.o_pin = al((size_t)n_seeds * sizeof(ActSeedDev));
-  L.o_frames = L.o_pin + al((size_t)std::max(n_pairs, 1) * sizeof(ActPairIn));
-  L.o_pout = L.o_frames + al((size_t)std::max(n_frames, 1) * sizeof(ActFrameDev));
-  L.o_jobs = L.o_pout + al((size_t)std::max(n_pairs, 1) * sizeof(ActPair));
-  L.o_match = L.o_jobs + al((size_t)std::max(n_pairs, 1) * sizeof(AlignJobDev));
-  L.o_out = L.o_match + al((size_t)std::max(n_pairs, 1) * sizeof(hso_align_out));
-  L.need = L.o_out + al((size_t)n_seeds * sizeof(hso_activate_out));
+  L.o_pin = hso_al256((size_t)n_seeds * sizeof(ActSeedDev));
+  L.o_frames = L.o_pin + hso_al256((size_t)std::max(n_pairs, 1) * sizeof(ActPairIn));
+  L.o_pout = L.o_frames + hso_al256((size_t)std::max(n_frames, 1) * sizeof(ActFrameDev));
+  L.o_jobs = L.o_pout + hso_al256((size_t)std::max(n_pairs, 1) * sizeof(ActPair));
+  L.o_match = L.o_jobs + hso_al256((size_t)std::max(n_pairs, 1) * sizeof(AlignJobDev));
+  L.o_out = L.o_match + hso_al256((size_t)std::max(n_pairs, 1) * sizeof(hso_align_out));
+  L.need = L.o_out + hso_al256((size_t)n_seeds * sizeof(hso_activate_out));
   return L;
 }
 static int act_match_pairs(hso_gpu_ctx* ctx, const hso_camera* cam, const PyrGeom& g, double z_min, char* d, const ActLayout& L, int n_pairs)
@@ -404,13 +403,7 @@ static int seed_activate_impl(hso_gpu_ctx* ctx, const hso_camera* cam, const hso
     }
   }
   if (cam->width != g.w[0] || cam->height != g.h[0]) return hso_fail(ctx, HSO_E_INVALID, "seed_activate: camera size differs from the frame size");
-  if (ctx->batch_cap < L.need) {
-    HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_batch) (void)hipFree(ctx->d_batch);
-    ctx->d_batch = nullptr; ctx->batch_cap = 0;
-    HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_batch), hso_grown(L.need)));
-    ctx->batch_cap = hso_grown(L.need);
-  }
+  if (int rc = hso_batch_reserve(ctx, L.need)) return rc;
   char* d = ctx->d_batch;
   HSO_HIP_CHECK(ctx, hipMemcpyAsync(d, h, L.o_pout, hipMemcpyHostToDevice, ctx->stream));
   if (int rc = act_match_pairs(ctx, cam, g, 0.0001, d, L, n_pairs)) return rc;
@@ -467,9 +460,8 @@ extern "C" int hso_gpu_seed_table_activate(hso_gpu_ctx* ctx, const hso_camera* c
   if (int rc = hso_seed_table_rows(ctx, table, slots, n_seeds, &rows, &stride, &seed_offset, &g)) return rc;
   const ActLayout L = act_layout(n_seeds, n_pairs, n_frames);
   // what crosses the bus: [frames | (slot, first, count, n_mean) per seed | 16-bit frame index per pair]
-  auto al = [](size_t v) { return (v + 255) & ~size_t(255); };
-  const size_t o_in = al((size_t)std::max(n_frames, 1) * sizeof(ActFrameDev)), o_pf = o_in + al((size_t)n_seeds * sizeof(ActSlotIn));
-  const size_t up_bytes = o_pf + al((size_t)std::max(n_pairs, 1) * sizeof(uint16_t));
+  const size_t o_in = hso_al256((size_t)std::max(n_frames, 1) * sizeof(ActFrameDev)), o_pf = o_in + hso_al256((size_t)n_seeds * sizeof(ActSlotIn));
+  const size_t up_bytes = o_pf + hso_al256((size_t)std::max(n_pairs, 1) * sizeof(uint16_t));
   char* h = hso_pinned(ctx, 0, up_bytes);
   if (!h) return HSO_E_NOMEM;
   ActFrameDev* hf = reinterpret_cast<ActFrameDev*>(h);
@@ -492,13 +484,7 @@ extern "C" int hso_gpu_seed_table_activate(hso_gpu_ctx* ctx, const hso_camera* c
   }
   if (cam->width != g.w[0] || cam->height != g.h[0]) return hso_fail(ctx, HSO_E_INVALID, "seed_table_activate: camera size differs from the frame size");
   const size_t need = L.need + up_bytes;
-  if (ctx->batch_cap < need) {
-    HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_batch) (void)hipFree(ctx->d_batch);
-    ctx->d_batch = nullptr; ctx->batch_cap = 0;
-    HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_batch), hso_grown(need)));
-    ctx->batch_cap = hso_grown(need);
-  }
+  if (int rc = hso_batch_reserve(ctx, need)) return rc;
   char* d = ctx->d_batch;
   char* d_up = d + L.need;
   HSO_HIP_CHECK(ctx, hipMemcpyAsync(d_up, h, up_bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -585,13 +571,7 @@ extern "C" int hso_gpu_seed_reproject_match(hso_gpu_ctx* ctx, const hso_camera* 
     hs[i].ref_base = itr->second.base; hs[i].s = seeds[i]; hs[i].first = i; hs[i].count = 1; hs[i].n_mean_converge_frame = 0; hs[i]._pad = 0;
     hp[i].seed = i; hp[i].frame = 0;
   }
-  if (ctx->batch_cap < L.need) {
-    HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_batch) (void)hipFree(ctx->d_batch);
-    ctx->d_batch = nullptr; ctx->batch_cap = 0;
-    HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_batch), hso_grown(L.need)));
-    ctx->batch_cap = hso_grown(L.need);
-  }
+  if (int rc = hso_batch_reserve(ctx, L.need)) return rc;
   char* d = ctx->d_batch;
   HSO_HIP_CHECK(ctx, hipMemcpyAsync(d, h, L.o_pout, hipMemcpyHostToDevice, ctx->stream));
   if (int rc = act_match_pairs(ctx, cam, g, 0.001, d, L, n_seeds)) return rc;

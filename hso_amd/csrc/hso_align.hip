@@ -124,15 +124,9 @@ static int align_run(hso_gpu_ctx* ctx, const hso_camera* cam, const int64_t* cur
     h[i].j = jobs[i];
   }
   if (cam->width != g.w[0] || cam->height != g.h[0]) return hso_fail(ctx, HSO_E_INVALID, "align_batch: camera size differs from the frame size");
-  const size_t b_jobs = ((size_t)n_jobs * sizeof(AlignJobDev) + 255) & ~size_t(255);
+  const size_t b_jobs = hso_al256((size_t)n_jobs * sizeof(AlignJobDev));
   const size_t need = b_jobs + (size_t)n_jobs * sizeof(hso_align_out);
-  if (ctx->batch_cap < need) {
-    HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_batch) (void)hipFree(ctx->d_batch);
-    ctx->d_batch = nullptr; ctx->batch_cap = 0;
-    HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_batch), hso_grown(need)));
-    ctx->batch_cap = hso_grown(need);
-  }
+  if (int rc = hso_batch_reserve(ctx, need)) return rc;
   AlignJobDev* d_jobs = reinterpret_cast<AlignJobDev*>(ctx->d_batch);
   hso_align_out* d_out = reinterpret_cast<hso_align_out*>(ctx->d_batch + b_jobs);
   HSO_HIP_CHECK(ctx, hipMemcpyAsync(d_jobs, h, (size_t)n_jobs * sizeof(AlignJobDev), hipMemcpyHostToDevice, ctx->stream));
@@ -350,22 +344,15 @@ extern "C" int hso_gpu_reproject_match_multi(hso_gpu_ctx* ctx, const hso_camera*
   for (int i = 0; i < n_points; i++)
     if (pt_frame[i] < 0) return hso_fail(ctx, HSO_E_INVALID, "reproject_match: a point belongs to no frame");
   if (cam->width != g.w[0] || cam->height != g.h[0]) return hso_fail(ctx, HSO_E_INVALID, "reproject_match: camera size differs from the frame size");
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t o_jobs = 0, o_out = o_jobs + al(sizeof(AlignJobDev) * (size_t)n_points);
-  const size_t o_proj = o_out + al(sizeof(hso_align_out) * (size_t)n_points);
-  const size_t o_kf = o_proj + al(sizeof(hso_reproj_point) * (size_t)n_points);
-  const size_t o_pts = o_kf + al(sizeof(ReprojKf) * (size_t)n_kfs);
-  const size_t o_obs = o_pts + al(sizeof(hso_map_point) * (size_t)n_points);
-  const size_t o_fr = o_obs + al(sizeof(hso_obs) * (size_t)(n_obs > 0 ? n_obs : 1));
-  const size_t o_pf = o_fr + al(sizeof(ReprojFrameDev) * (size_t)n_frames);
-  const size_t need = o_pf + al(sizeof(int) * (size_t)n_points);
-  if (ctx->batch_cap < need) {
-    HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_batch) (void)hipFree(ctx->d_batch);
-    ctx->d_batch = nullptr; ctx->batch_cap = 0;
-    HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_batch), hso_grown(need)));
-    ctx->batch_cap = hso_grown(need);
-  }
+  const size_t o_jobs = 0, o_out = o_jobs + hso_al256(sizeof(AlignJobDev) * (size_t)n_points);
+  const size_t o_proj = o_out + hso_al256(sizeof(hso_align_out) * (size_t)n_points);
+  const size_t o_kf = o_proj + hso_al256(sizeof(hso_reproj_point) * (size_t)n_points);
+  const size_t o_pts = o_kf + hso_al256(sizeof(ReprojKf) * (size_t)n_kfs);
+  const size_t o_obs = o_pts + hso_al256(sizeof(hso_map_point) * (size_t)n_points);
+  const size_t o_fr = o_obs + hso_al256(sizeof(hso_obs) * (size_t)(n_obs > 0 ? n_obs : 1));
+  const size_t o_pf = o_fr + hso_al256(sizeof(ReprojFrameDev) * (size_t)n_frames);
+  const size_t need = o_pf + hso_al256(sizeof(int) * (size_t)n_points);
+  if (int rc = hso_batch_reserve(ctx, need)) return rc;
   char* d = ctx->d_batch;
   // Small calls (one keyframe-sized sequence) are latency-bound: one pinned staging image of
   // [kf | points | obs | frames | point->frame] and one DMA each way.  Large multi-sequence tables
@@ -584,20 +571,12 @@ static_assert(sizeof(hso_map_point) % 8 == 0 && sizeof(hso_obs) % 8 == 0, "rows 
 // grow-only device array: new memory is filled with `fill` bytes, the first `keep` elements are carried over
 template <typename T> static int seqmap_grow(hso_gpu_ctx* ctx, T** p, size_t* cap, size_t need, size_t keep, int fill = 0, size_t min_cap = 65536)
 {
-  if (*cap >= need) return HSO_OK;
   // a growth = allocation + fill + copy + a wait for the stream: with one map per sequence and hundreds of sequences growing in step
   // with their keyframes, small increments meant ten growths per step of 128 sequences.  So: room for a dozen keyframes' rows at
   // once (a few MB per map of 288 GB), doubling after that.
-  const size_t ncap = std::max(need * 2, min_cap);
-  T* q = nullptr;
-  HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&q), ncap * sizeof(T)));
-  hipError_t e = hipMemsetAsync(q, fill, ncap * sizeof(T), ctx->stream);
-  if (e == hipSuccess && *p && keep) e = hipMemcpyAsync(q, *p, keep * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) { (void)hipFree(q); ctx->err = std::string("seqmap: ") + hipGetErrorString(e); return HSO_E_HIP; }
-  if (*p) (void)hipFree(*p);
-  *p = q; *cap = ncap;
-  return HSO_OK;
+  const int rc = hso_dev_grow_keep(ctx, p, cap, need, keep, std::max(need * 2, min_cap), fill);
+  if (rc) ctx->err = "seqmap: " + ctx->err;
+  return rc;
 }
 
 // the tables that grow in step with the point / observation tables
@@ -608,17 +587,6 @@ static int seqmap_grow_tables(hso_gpu_ctx* ctx, SeqMap* m, size_t need_pts, size
   if (int rc = seqmap_grow(ctx, &m->d_first, &m->first_cap, m->pts_cap, 0, 0x7f)) return rc;          // never holds state between calls
   if (int rc = seqmap_grow(ctx, &m->d_obs, &m->obs_cap, need_obs, m->n_obs)) return rc;
   if (int rc = seqmap_grow(ctx, &m->d_obs_pt, &m->obs_pt_cap, m->obs_cap, m->n_obs, 0xff)) return rc;  // -1: no point
-  return HSO_OK;
-}
-
-static int seqmap_work_area(hso_gpu_ctx* ctx, size_t need)
-{
-  if (ctx->batch_cap >= need) return HSO_OK;
-  HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->d_batch) (void)hipFree(ctx->d_batch);
-  ctx->d_batch = nullptr; ctx->batch_cap = 0;
-  HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_batch), hso_grown(need)));
-  ctx->batch_cap = hso_grown(need);
   return HSO_OK;
 }
 
@@ -669,13 +637,7 @@ int hso_seqmap_flush_kfs(hso_gpu_ctx* ctx)
   if (rows.empty()) { mark_clean(); return HSO_OK; }
   HSO_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const size_t row_bytes = sizeof(SeqKfDev) * rows.size(), need = row_bytes + sizeof(void*) * rows.size();
-  if (S->kfup_cap < need) {
-    HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (S->d_kfup) (void)hipFree(S->d_kfup);
-    S->d_kfup = nullptr; S->kfup_cap = 0;
-    HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&S->d_kfup), hso_grown(need)));
-    S->kfup_cap = hso_grown(need);
-  }
+  if (int rc = hso_dev_reserve(ctx, ctx->stream, &S->d_kfup, &S->kfup_cap, need)) return rc;
   // staged by the copy wrapper: the vectors may go when this returns
   std::vector<char> image(need);
   memcpy(image.data(), rows.data(), row_bytes); memcpy(image.data() + row_bytes, dst.data(), sizeof(void*) * rows.size());
@@ -807,15 +769,14 @@ int hso_gpu_seqmap_patch_multi(hso_gpu_ctx* ctx, const hso_seqmap_rows* patches,
   tp = at_p.back(); to = at_o.back();
   if (tp + to == 0) return HSO_OK;
   HSO_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
   // [destination row pointers of the points | of the observations | of the links | point rows | observation rows | links]
   const size_t tl = at_l.back();
-  const size_t b_dp = al(sizeof(void*) * tp), b_do = al(sizeof(void*) * to), b_dl = al(sizeof(void*) * tl);
-  const size_t b_p = al(sizeof(hso_map_point) * tp), b_o = al(sizeof(hso_obs) * to), b_l = al(sizeof(int32_t) * tl);
+  const size_t b_dp = hso_al256(sizeof(void*) * tp), b_do = hso_al256(sizeof(void*) * to), b_dl = hso_al256(sizeof(void*) * tl);
+  const size_t b_p = hso_al256(sizeof(hso_map_point) * tp), b_o = hso_al256(sizeof(hso_obs) * to), b_l = hso_al256(sizeof(int32_t) * tl);
   const size_t need = b_dp + b_do + b_dl + b_p + b_o + b_l;
   // the image is assembled in the stream's page-locked staging chunks and leaves with one DMA: no wait for the copy here — a step
   // patches before its chain call, whose own synchronisation releases the chunks
-  if (int rc = seqmap_work_area(ctx, need)) return rc;
+  if (int rc = hso_batch_reserve(ctx, need)) return rc;
   char* h = hso_stage_reserve(ctx->stream, need);
   if (!h) return hso_fail(ctx, HSO_E_NOMEM, "seqmap_patch: no staging memory");
   hso_map_point** dp = reinterpret_cast<hso_map_point**>(h);
@@ -859,8 +820,8 @@ int hso_gpu_seqmap_patch_links(hso_gpu_ctx* ctx, int map, const int32_t* obs_ids
     if (obs_ids[i] < 0 || (size_t)obs_ids[i] >= m->n_obs || obs_point[i] < -1 || (obs_point[i] >= 0 && (size_t)obs_point[i] >= m->n_pts))
       return hso_fail(ctx, HSO_E_INVALID, "seqmap_patch_links: row out of range");
   HSO_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const size_t b_id = ((size_t)n_obs * sizeof(int32_t) + 255) & ~size_t(255);
-  if (int rc = seqmap_work_area(ctx, 2 * b_id)) return rc;
+  const size_t b_id = hso_al256((size_t)n_obs * sizeof(int32_t));
+  if (int rc = hso_batch_reserve(ctx, 2 * b_id)) return rc;
   char* d = ctx->d_batch;
   HSO_HIP_CHECK(ctx, hipMemcpyAsync(d, obs_ids, sizeof(int32_t) * (size_t)n_obs, hipMemcpyHostToDevice, ctx->stream));
   HSO_HIP_CHECK(ctx, hipMemcpyAsync(d + b_id, obs_point, sizeof(int32_t) * (size_t)n_obs, hipMemcpyHostToDevice, ctx->stream));
@@ -901,8 +862,7 @@ int hso_gpu_seqmap_patch_lists(hso_gpu_ctx* ctx, const hso_seqmap_list_patch* pa
   }
   if (total > 0) {
     HSO_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t b_d = al(sizeof(void*) * total), need = b_d + al(sizeof(int32_t) * total);
+    const size_t b_d = hso_al256(sizeof(void*) * total), need = b_d + hso_al256(sizeof(int32_t) * total);
     std::vector<char> img(need);
     int32_t** dst = reinterpret_cast<int32_t**>(img.data());
     int32_t* val = reinterpret_cast<int32_t*>(img.data() + b_d);
@@ -913,7 +873,7 @@ int hso_gpu_seqmap_patch_lists(hso_gpu_ctx* ctx, const hso_seqmap_list_patch* pa
       int32_t* base = P.list == HSO_LIST_CANDIDATES ? m->d_cands : m->d_kf_fts + (size_t)P.list * (size_t)m->fts_cap;
       for (int k = 0; k < P.n; k++) { dst[at] = base + P.first + k; val[at] = P.ids[k]; at++; }
     }
-    if (int rc = seqmap_work_area(ctx, need)) return rc;
+    if (int rc = hso_batch_reserve(ctx, need)) return rc;
     HSO_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_batch, img.data(), need, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_scatter_ints_to, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream,
                        reinterpret_cast<int32_t* const*>(ctx->d_batch), reinterpret_cast<const int32_t*>(ctx->d_batch + b_d), (int)total);
@@ -949,10 +909,9 @@ int hso_gpu_seqmap_read(hso_gpu_ctx* ctx, int map, const int32_t* point_ids, int
   for (int i = 0; i < n_obs; i++) if (obs_ids[i] < 0 || (size_t)obs_ids[i] >= m->n_obs) return hso_fail(ctx, HSO_E_INVALID, "seqmap_read: observation id out of range");
   if (n_points == 0 && n_obs == 0) return HSO_OK;
   HSO_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t b_pid = al(sizeof(int) * (size_t)n_points), b_pts = al(sizeof(hso_map_point) * (size_t)n_points);
-  const size_t b_oid = al(sizeof(int) * (size_t)n_obs), b_obs = al(sizeof(hso_obs) * (size_t)n_obs);
-  if (int rc = seqmap_work_area(ctx, b_pid + b_pts + b_oid + b_obs)) return rc;
+  const size_t b_pid = hso_al256(sizeof(int) * (size_t)n_points), b_pts = hso_al256(sizeof(hso_map_point) * (size_t)n_points);
+  const size_t b_oid = hso_al256(sizeof(int) * (size_t)n_obs), b_obs = hso_al256(sizeof(hso_obs) * (size_t)n_obs);
+  if (int rc = hso_batch_reserve(ctx, b_pid + b_pts + b_oid + b_obs)) return rc;
   char* d = ctx->d_batch;
   if (n_points) {
     HSO_HIP_CHECK(ctx, hipMemcpyAsync(d, point_ids, sizeof(int) * (size_t)n_points, hipMemcpyHostToDevice, ctx->stream));

@@ -893,43 +893,42 @@ static void ba_layout(BaWin& B, int n_poses, int n_points, const uint8_t* pose_f
   B.M = 6 * n_free;
   B.n_free = n_free; B.n_bins = n_free * (n_free + 1) / 2; B.n_chunks = (n_edges + RBA_CHUNK - 1) / RBA_CHUNK;
 
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
   size_t o = 0;
   // [lambda | xc | pad | poses | fixed | col]: the trial block first, the state right behind it; then what only goes up
-  B.o_trial = o; o += al(sizeof(double) * (2 + 6 * (size_t)n_poses));   // lambda, xc, "no step" flag
-  B.o_poses = o; o += al(sizeof(hso_se3) * n_poses);
-  B.o_fixed = o; o += al(n_poses);
-  B.o_col = o; o += al(sizeof(int) * n_poses);
+  B.o_trial = o; o += hso_al256(sizeof(double) * (2 + 6 * (size_t)n_poses));   // lambda, xc, "no step" flag
+  B.o_poses = o; o += hso_al256(sizeof(hso_se3) * n_poses);
+  B.o_fixed = o; o += hso_al256(n_poses);
+  B.o_col = o; o += hso_al256(sizeof(int) * n_poses);
   B.small_bytes = resident ? o : 0;
-  B.o_idist = o; o += al(sizeof(double) * n_points);
-  B.o_edges = o; o += al(sizeof(hso_ba_edge) * n_edges);
-  B.o_off = o; o += al(sizeof(int) * (n_points + 1));
-  B.o_list = o; o += al(sizeof(int) * n_edges);
-  B.o_poff = o; o += al(sizeof(int) * (n_pairs + 1));
-  B.o_plist = o; o += al(sizeof(int) * 3 * (size_t)n_edges);
-  B.o_uv = o; if (with_uv) o += al(sizeof(double) * 2 * (size_t)n_edges);
-  B.o_eobs = o; if (resident) o += al(sizeof(int) * (size_t)n_edges);
+  B.o_idist = o; o += hso_al256(sizeof(double) * n_points);
+  B.o_edges = o; o += hso_al256(sizeof(hso_ba_edge) * n_edges);
+  B.o_off = o; o += hso_al256(sizeof(int) * (n_points + 1));
+  B.o_list = o; o += hso_al256(sizeof(int) * n_edges);
+  B.o_poff = o; o += hso_al256(sizeof(int) * (n_pairs + 1));
+  B.o_plist = o; o += hso_al256(sizeof(int) * 3 * (size_t)n_edges);
+  B.o_uv = o; if (with_uv) o += hso_al256(sizeof(double) * 2 * (size_t)n_edges);
+  B.o_eobs = o; if (resident) o += hso_al256(sizeof(int) * (size_t)n_edges);
   B.in_bytes = o;
-  B.o_lin = o; o += al(sizeof(double) * BA_LIN * n_edges);
-  B.o_rho = o; o += al(sizeof(double) * n_edges);
+  B.o_lin = o; o += hso_al256(sizeof(double) * BA_LIN * n_edges);
+  B.o_rho = o; o += hso_al256(sizeof(double) * n_edges);
   B.o_out = o;
-  B.o_Hpp = o; o += al(sizeof(double) * n_points);
-  B.o_bp = o; o += al(sizeof(double) * n_points);
-  B.o_Hpc = o; o += al(sizeof(double) * (size_t)n_points * n_poses * 6);
-  B.o_Hcc = o; o += al(sizeof(double) * (size_t)n_poses * n_poses * 36);
-  B.o_bc = o; o += al(sizeof(double) * n_poses * 6);
-  B.o_err = o; o += al(sizeof(double) * 2 * n_edges);
-  B.o_chi = o; o += al(sizeof(double) * n_edges);
+  B.o_Hpp = o; o += hso_al256(sizeof(double) * n_points);
+  B.o_bp = o; o += hso_al256(sizeof(double) * n_points);
+  B.o_Hpc = o; o += hso_al256(sizeof(double) * (size_t)n_points * n_poses * 6);
+  B.o_Hcc = o; o += hso_al256(sizeof(double) * (size_t)n_poses * n_poses * 36);
+  B.o_bc = o; o += hso_al256(sizeof(double) * n_poses * 6);
+  B.o_err = o; o += hso_al256(sizeof(double) * 2 * n_edges);
+  B.o_chi = o; o += hso_al256(sizeof(double) * n_edges);
   // the reduced system of a trial: S, the "solvable" flag behind it, rhs (they stay on the device)
   B.o_sum = o; o += 256;
   B.o_S = o; o += sizeof(double) * ((size_t)B.M * B.M + 1);
   B.o_rhs = o; o += sizeof(double) * (size_t)B.M;
-  o = al(o);
-  B.o_xp = o; o += al(sizeof(double) * n_points);
-  B.o_bak = o; o += al(sizeof(double) * n_points);
-  B.o_pbak = o; o += al(sizeof(hso_se3) * n_poses);
-  B.o_pcnt = o; if (resident) o += al(sizeof(int) * ((size_t)B.n_chunks + 1) * (size_t)std::max(B.n_bins, 1));
-  B.o_cull = o; if (resident) o += al(sizeof(int) * (2 + (size_t)n_edges));
+  o = hso_al256(o);
+  B.o_xp = o; o += hso_al256(sizeof(double) * n_points);
+  B.o_bak = o; o += hso_al256(sizeof(double) * n_points);
+  B.o_pbak = o; o += hso_al256(sizeof(hso_se3) * n_poses);
+  B.o_pcnt = o; if (resident) o += hso_al256(sizeof(int) * ((size_t)B.n_chunks + 1) * (size_t)std::max(B.n_bins, 1));
+  B.o_cull = o; if (resident) o += hso_al256(sizeof(int) * (2 + (size_t)n_edges));
   B.total = o;
 }
 
@@ -986,21 +985,14 @@ static int ba_batch_begin(BaBatch& Q, hso_gpu_ctx* ctx, const hso_ba_problem* pr
 {
   Q.ctx = ctx; Q.n = n;
   HSO_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t o_act = al(sizeof(BaProb) * (size_t)n), o_lam = o_act + al(sizeof(BaLmDev) * (size_t)n);
-  const size_t o_sums = o_lam + al(sizeof(double) * (size_t)n);
-  const size_t o_hub = o_sums + al(sizeof(double) * 8 * (size_t)n);
-  const size_t o_extra = o_hub + al(sizeof(float) * 2 * (size_t)n);
-  size_t dev = o_extra + al(res ? res->extra_hdr : 0), pin_in = dev;
+  const size_t o_act = hso_al256(sizeof(BaProb) * (size_t)n), o_lam = o_act + hso_al256(sizeof(BaLmDev) * (size_t)n);
+  const size_t o_sums = o_lam + hso_al256(sizeof(double) * (size_t)n);
+  const size_t o_hub = o_sums + hso_al256(sizeof(double) * 8 * (size_t)n);
+  const size_t o_extra = o_hub + hso_al256(sizeof(float) * 2 * (size_t)n);
+  size_t dev = o_extra + hso_al256(res ? res->extra_hdr : 0), pin_in = dev;
   const size_t hdr = dev;
   for (int q = 0; q < n; q++) { dev += Q.win[q].total; pin_in += res ? Q.win[q].small_bytes : Q.win[q].in_bytes; }
-  if (ctx->batch_cap < dev) {  // grow-only work area of the context (shared with the other batched entry points)
-    HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_batch) (void)hipFree(ctx->d_batch);
-    ctx->d_batch = nullptr; ctx->batch_cap = 0;
-    HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_batch), hso_grown(dev)));
-    ctx->batch_cap = hso_grown(dev);
-  }
+  if (int rc = hso_batch_reserve(ctx, dev)) return rc;  // grow-only work area of the context (shared with the other batched entry points)
   char* d = reinterpret_cast<char*>(ctx->d_batch);
   char* h = hso_pinned(ctx, 0, pin_in);
   if (!h) return HSO_E_NOMEM;
@@ -1245,11 +1237,10 @@ extern "C" int hso_gpu_ba_huber_deltas_multi(hso_gpu_ctx* ctx, hso_ba_deltas_job
 {
   if (!ctx) return HSO_E_INVALID;
   if (n_jobs < 0 || (n_jobs > 0 && !jobs)) return hso_fail(ctx, HSO_E_INVALID, "ba_huber_deltas: bad argument");
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
   struct Lay { size_t o_poses, o_idist, o_edges, o_uv, o_err; };
   std::vector<Lay> lay((size_t)n_jobs);
   std::vector<int> live;
-  size_t o = al(sizeof(MadWin) * (size_t)std::max(n_jobs, 1));
+  size_t o = hso_al256(sizeof(MadWin) * (size_t)std::max(n_jobs, 1));
   int max_edges = 0;
   for (int j = 0; j < n_jobs; j++) {
     hso_ba_deltas_job& J = jobs[j];
@@ -1258,10 +1249,10 @@ extern "C" int hso_gpu_ba_huber_deltas_multi(hso_gpu_ctx* ctx, hso_ba_deltas_job
     J.huber_corner = 0; J.huber_edge = 0;
     if (J.n_edges == 0) continue;   // both error lists empty: the reference leaves the deltas uninitialised
     Lay& L = lay[(size_t)j];
-    L.o_poses = o; o += al(sizeof(hso_se3) * (size_t)J.n_poses);
-    L.o_idist = o; o += al(sizeof(double) * (size_t)J.n_points);
-    L.o_edges = o; o += al(sizeof(hso_ba_edge) * (size_t)J.n_edges);
-    L.o_uv = o; o += al(sizeof(double) * 2 * (size_t)J.n_edges);
+    L.o_poses = o; o += hso_al256(sizeof(hso_se3) * (size_t)J.n_poses);
+    L.o_idist = o; o += hso_al256(sizeof(double) * (size_t)J.n_points);
+    L.o_edges = o; o += hso_al256(sizeof(hso_ba_edge) * (size_t)J.n_edges);
+    L.o_uv = o; o += hso_al256(sizeof(double) * 2 * (size_t)J.n_edges);
     live.push_back(j); max_edges = std::max(max_edges, (int)J.n_edges);
   }
   if (live.empty()) return HSO_OK;
@@ -1275,16 +1266,10 @@ extern "C" int hso_gpu_ba_huber_deltas_multi(hso_gpu_ctx* ctx, hso_ba_deltas_job
       if (bad[w]) { const hso_ba_deltas_job& J = jobs[live[w]]; return ba_check_edges(ctx, J.edges, J.n_edges, J.n_points, J.n_poses, "ba_huber_deltas"); }
   }
   const size_t in_bytes = o;
-  for (int j : live) { lay[(size_t)j].o_err = o; o += al(sizeof(float) * (size_t)jobs[j].n_edges); }
+  for (int j : live) { lay[(size_t)j].o_err = o; o += hso_al256(sizeof(float) * (size_t)jobs[j].n_edges); }
   const size_t err_bytes = o - in_bytes;
   HSO_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (ctx->batch_cap < o) {
-    HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_batch) (void)hipFree(ctx->d_batch);
-    ctx->d_batch = nullptr; ctx->batch_cap = 0;
-    HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_batch), hso_grown(o)));
-    ctx->batch_cap = hso_grown(o);
-  }
+  if (int rc = hso_batch_reserve(ctx, o)) return rc;
   char* d = reinterpret_cast<char*>(ctx->d_batch);
   char* h = hso_pinned(ctx, 0, in_bytes);
   char* he = hso_pinned(ctx, 1, err_bytes);
@@ -1849,7 +1834,6 @@ extern "C" int hso_gpu_seq_local_ba(hso_gpu_ctx* ctx, const hso_seq_ba_job* jobs
   if (ctx->rba_last) ctx->rba_last->win.clear();
   if (n_jobs == 0) return HSO_OK;
   HSO_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
   // ---- the jobs against their maps; the per-job tables of stage A
   std::vector<SeqMapDev> view((size_t)n_jobs);
   std::vector<const hso_kf*> kfs_host((size_t)n_jobs);
@@ -1878,33 +1862,27 @@ extern "C" int hso_gpu_seq_local_ba(hso_gpu_ctx* ctx, const hso_seq_ba_job* jobs
     }
     J.nb = (int)std::min<size_t>(len, (size_t)M.n_pts);
     max_core = std::max(max_core, A.n_core); max_nb = std::max(max_nb, J.nb);
-    zero_bytes += al(sizeof(int32_t) * (size_t)M.n_pts);
-    ones_bytes += al(sizeof(unsigned long long) * (size_t)M.n_kfs) + al(sizeof(int32_t) * (size_t)M.n_kfs);
-    rest_bytes += al(sizeof(int32_t) * (size_t)J.nb) + al(sizeof(int32_t) * ((size_t)J.nb + 1)) + al(sizeof(double) * (size_t)J.nb) + al(sizeof(double) * 4 * (size_t)J.nb);
+    zero_bytes += hso_al256(sizeof(int32_t) * (size_t)M.n_pts);
+    ones_bytes += hso_al256(sizeof(unsigned long long) * (size_t)M.n_kfs) + hso_al256(sizeof(int32_t) * (size_t)M.n_kfs);
+    rest_bytes += hso_al256(sizeof(int32_t) * (size_t)J.nb) + hso_al256(sizeof(int32_t) * ((size_t)J.nb + 1)) + hso_al256(sizeof(double) * (size_t)J.nb) + hso_al256(sizeof(double) * 4 * (size_t)J.nb);
   }
   const size_t sz_bytes = sizeof(int32_t) * RBA_SIZES * (size_t)n_jobs;   // the jobs' sizes side by side: one copy brings them
-  const size_t o_jobs = 0, o_sizes = al(sizeof(RbaJobDev) * (size_t)n_jobs), o_zero = o_sizes + al(sz_bytes), o_ones = o_zero + zero_bytes, o_rest = o_ones + ones_bytes,
+  const size_t o_jobs = 0, o_sizes = hso_al256(sizeof(RbaJobDev) * (size_t)n_jobs), o_zero = o_sizes + hso_al256(sz_bytes), o_ones = o_zero + zero_bytes, o_rest = o_ones + ones_bytes,
                need = o_rest + rest_bytes;
-  if (ctx->rba_cap < need) {
-    HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_rba) (void)hipFree(ctx->d_rba);
-    ctx->d_rba = nullptr; ctx->rba_cap = 0;
-    HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_rba), hso_grown(need)));
-    ctx->rba_cap = hso_grown(need);
-  }
+  if (int rc = hso_dev_reserve(ctx, ctx->stream, &ctx->d_rba, &ctx->rba_cap, need)) return rc;
   char* dr = ctx->d_rba;
   {
     size_t z = o_zero, o = o_ones, r = o_rest;
     for (int j = 0; j < n_jobs; j++) {
       RbaJobDev& J = hj[(size_t)j];
-      J.mark = reinterpret_cast<int32_t*>(dr + z); z += al(sizeof(int32_t) * (size_t)J.n_pts);
-      J.fkey = reinterpret_cast<unsigned long long*>(dr + o); o += al(sizeof(unsigned long long) * (size_t)J.n_kfs);
-      J.vtx = reinterpret_cast<int32_t*>(dr + o); o += al(sizeof(int32_t) * (size_t)J.n_kfs);
-      J.ids = reinterpret_cast<int32_t*>(dr + r); r += al(sizeof(int32_t) * (size_t)J.nb);
-      J.eoff = reinterpret_cast<int32_t*>(dr + r); r += al(sizeof(int32_t) * ((size_t)J.nb + 1));
+      J.mark = reinterpret_cast<int32_t*>(dr + z); z += hso_al256(sizeof(int32_t) * (size_t)J.n_pts);
+      J.fkey = reinterpret_cast<unsigned long long*>(dr + o); o += hso_al256(sizeof(unsigned long long) * (size_t)J.n_kfs);
+      J.vtx = reinterpret_cast<int32_t*>(dr + o); o += hso_al256(sizeof(int32_t) * (size_t)J.n_kfs);
+      J.ids = reinterpret_cast<int32_t*>(dr + r); r += hso_al256(sizeof(int32_t) * (size_t)J.nb);
+      J.eoff = reinterpret_cast<int32_t*>(dr + r); r += hso_al256(sizeof(int32_t) * ((size_t)J.nb + 1));
       J.sizes = reinterpret_cast<int32_t*>(dr + o_sizes) + RBA_SIZES * (size_t)j;
-      J.idist0 = reinterpret_cast<double*>(dr + r); r += al(sizeof(double) * (size_t)J.nb);
-      J.state = reinterpret_cast<double*>(dr + r); r += al(sizeof(double) * 4 * (size_t)J.nb);
+      J.idist0 = reinterpret_cast<double*>(dr + r); r += hso_al256(sizeof(double) * (size_t)J.nb);
+      J.state = reinterpret_cast<double*>(dr + r); r += hso_al256(sizeof(double) * 4 * (size_t)J.nb);
     }
   }
   char* hp0 = hso_pinned(ctx, 0, sizeof(RbaJobDev) * (size_t)n_jobs);

@@ -163,6 +163,39 @@ template <class F> void hso_host_parallel(hso_gpu_ctx* ctx, int n, size_t work, 
 // size of a grow-only buffer that must hold `need` bytes now: half again as much + 1 MB, so that tables that grow a little with
 // every keyframe do not re-allocate (hipFree synchronises the device: 0.2-0.4 ms each, 18 per step at 32 sequences before this)
 inline size_t hso_grown(size_t need) { return need + need / 2 + (size_t(1) << 20); }
+inline size_t hso_al256(size_t b) { return (b + 255) & ~size_t(255); }   // regions of a work area start 256-byte aligned
+// The one way a call obtains a grow-only device buffer of at least `need` bytes.  Nothing happens while *cap >= need.  Otherwise
+// the CONTENTS ARE LOST: waits for `stream` (idle afterwards: nothing queued on it still reads the old buffer), frees, leaves
+// *p / *cap null / 0 (what a failed allocation leaves behind: an empty buffer, not a dangling one), then allocates
+// new_cap ? new_cap : hso_grown(need) bytes and records that as the capacity.  Capacity is never reduced.  A HIP error sets
+// ctx->err, abandons ctx->stream as HSO_HIP_CHECK does and returns HSO_E_HIP.  Does not select the device.
+int hso_dev_reserve(hso_gpu_ctx* ctx, hipStream_t stream, char** p, size_t* cap, size_t need, size_t new_cap = 0);
+// ... the per-call work area every batched entry point carves its tables out of (shared: no call's contents outlive the call)
+inline int hso_batch_reserve(hso_gpu_ctx* ctx, size_t need) { return hso_dev_reserve(ctx, ctx->stream, &ctx->d_batch, &ctx->batch_cap, need); }
+// The same for a grow-only device array whose CONTENTS STAY (cap, need, keep, new_cap in elements; the caller supplies its growth
+// rule as new_cap): nothing while *cap >= need; otherwise new memory of new_cap elements, every byte of it set to `fill` (-1: left
+// as allocated), the first `keep` elements copied over on ctx->stream, then a wait for the stream, the old array freed and the new
+// one in its place.  A failure frees the new array and leaves the old one as it was.
+template <typename T> int hso_dev_grow_keep(hso_gpu_ctx* ctx, T** p, size_t* cap, size_t need, size_t keep, size_t new_cap, int fill = -1)
+{
+  if (*cap >= need) return HSO_OK;
+  T* q = nullptr;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&q), new_cap * sizeof(T));
+  const char* what = e == hipSuccess ? "dev_grow_keep: fill, copy and wait" : "dev_grow_keep: device allocation";
+  if (e != hipSuccess) q = nullptr;
+  if (e == hipSuccess && fill >= 0) e = hso_memset_async(q, fill, new_cap * sizeof(T), ctx->stream);
+  if (e == hipSuccess && *p && keep) e = hso_copy_async(q, *p, keep * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream);
+  if (e == hipSuccess) e = hso_stream_sync(ctx->stream);   // also with nothing to copy: work queued earlier may still read the old array
+  if (e != hipSuccess) {
+    if (q) (void)hipFree(q);
+    ctx->err = std::string(what) + ": " + hipGetErrorString(e);
+    hso_stream_abandon(ctx->stream);
+    return HSO_E_HIP;
+  }
+  if (*p) (void)hipFree(*p);
+  *p = q; *cap = new_cap;
+  return HSO_OK;
+}
 // pinned staging buffer `slot` (0: inputs, 1: results) of at least `bytes`; nullptr if the allocation fails.
 // Contents are only valid until the next call that uses the slot; every entry point synchronises before it returns.
 char* hso_pinned(hso_gpu_ctx* ctx, int slot, size_t bytes);

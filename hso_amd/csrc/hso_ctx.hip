@@ -44,7 +44,7 @@ bool host_is_page_locked(const void* p)
 
 char* stage_alloc(Stager& S, size_t bytes)
 {
-  const size_t need = (bytes + 255) & ~size_t(255);
+  const size_t need = hso_al256(bytes);
   for (StageChunk& c : S.chunks)
     if (c.cap - c.used >= need) { char* r = c.p + c.used; c.used += need; return r; }
   StageChunk c{nullptr, std::max(need, size_t(8) << 20), 0};
@@ -241,6 +241,24 @@ int hso_fail(hso_gpu_ctx* ctx, int code, const char* msg)
   return code;
 }
 
+// see hso_ctx.h
+int hso_dev_reserve(hso_gpu_ctx* ctx, hipStream_t stream, char** p, size_t* cap, size_t need, size_t new_cap)
+{
+  if (*cap >= need) return HSO_OK;
+  auto fail = [&](const char* what, hipError_t e) {
+    ctx->err = std::string(what) + ": " + hipGetErrorString(e);
+    hso_stream_abandon(ctx->stream);
+    return HSO_E_HIP;
+  };
+  if (hipError_t e = hipStreamSynchronize(stream)) return fail("dev_reserve: waiting for the stream", e);   // the old buffer stays
+  if (*p) (void)hipFree(*p);
+  *p = nullptr; *cap = 0;
+  if (!new_cap) new_cap = hso_grown(need);
+  if (hipError_t e = hipMalloc(reinterpret_cast<void**>(p), new_cap)) { *p = nullptr; return fail("dev_reserve: device allocation", e); }
+  *cap = new_cap;
+  return HSO_OK;
+}
+
 // Frame storage comes in slabs: the device allocator takes 0.1-0.2 ms per call on this stack, and a bank of 64 sequences
 // constructs 64 frames per step (10 ms of a step went into 64 hipMalloc calls until the first frames were released).  A slab
 // holds HSO_FRAMES_PER_SLAB frames of one geometry; pieces are handed out and returned through the free list of that geometry and
@@ -256,7 +274,7 @@ int hso_frame_alloc(hso_gpu_ctx* ctx, const PyrGeom& g, uint8_t** base)
     return HSO_OK;
   }
   *base = nullptr;
-  const size_t stride = ((size_t)g.frame_bytes + 255) & ~size_t(255);
+  const size_t stride = hso_al256(g.frame_bytes);
   uint8_t* slab = nullptr;
   HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&slab), stride * HSO_FRAMES_PER_SLAB));
   ctx->frame_slabs.push_back(slab);
@@ -383,16 +401,8 @@ extern "C++" int hso_frame_require_gradients(hso_gpu_ctx* ctx, const int64_t* fr
   // frames of one geometry next to each other: one launch each
   std::stable_sort(todo.begin(), todo.end(), [](const FrameRec* a, const FrameRec* b) { return geom_key(a->g) < geom_key(b->g); });
   const size_t need = todo.size() * sizeof(uint8_t*);
-  if (ctx->batch_cap < need) {   // (only ever the first call of a context: every batched entry point sizes this area for more)
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) {
-      if (ctx->d_batch) (void)hipFree(ctx->d_batch);
-      ctx->d_batch = nullptr; ctx->batch_cap = 0;
-      e = hipMalloc(reinterpret_cast<void**>(&ctx->d_batch), hso_grown(need));
-    }
-    if (e != hipSuccess) { undo(); HSO_HIP_CHECK(ctx, e); }
-    ctx->batch_cap = hso_grown(need);
-  }
+  // (grows only ever in the first call of a context: every batched entry point sizes this area for more)
+  if (int rc = hso_batch_reserve(ctx, need)) { undo(); return rc; }
   std::vector<uint8_t*> bases(todo.size());
   for (size_t i = 0; i < todo.size(); i++) bases[i] = todo[i]->base;
   uint8_t** d_bases = reinterpret_cast<uint8_t**>(ctx->d_batch);
@@ -436,23 +446,20 @@ int hso_lists_to_host(hso_gpu_ctx* ctx, const std::vector<HsoListCopy>& lists)
   for (const HsoListCopy& c : lists) if (c.bytes > 0) live.push_back(&c);
   if (live.empty()) { HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream)); return HSO_OK; }
   const size_t n = live.size();
-  const size_t tab = (sizeof(ListRec) * n + 255) & ~size_t(255);
+  const size_t tab = hso_al256(sizeof(ListRec) * n);
   size_t words = 0, longest = 0;
   for (const HsoListCopy* c : live) {
     if ((c->bytes & 3) || (reinterpret_cast<uintptr_t>(c->src) & 3)) return hso_fail(ctx, HSO_E_INVALID, "lists_to_host: list not in 4-byte units");
     words += c->bytes / 4; longest = std::max(longest, c->bytes / 4);
   }
   const size_t need = tab + words * 4;
-  if (ctx->d_pack_cap < need || ctx->h_pack_cap < need) {
+  if (int rc = hso_dev_reserve(ctx, ctx->stream, &ctx->d_pack, &ctx->d_pack_cap, need)) return rc;
+  if (ctx->h_pack_cap < need) {   // the page-locked half (the two grow together: both capacities are hso_grown of the same need)
     HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_pack) (void)hipFree(ctx->d_pack);
     if (ctx->h_pack) (void)hipHostFree(ctx->h_pack);
-    ctx->d_pack = nullptr; ctx->h_pack = nullptr; ctx->d_pack_cap = ctx->h_pack_cap = 0;
-    const size_t cap = hso_grown(need);
-    HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_pack), cap));
-    ctx->d_pack_cap = cap;
-    HSO_HIP_CHECK(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->h_pack), cap, hipHostMallocDefault));
-    ctx->h_pack_cap = cap;
+    ctx->h_pack = nullptr; ctx->h_pack_cap = 0;
+    HSO_HIP_CHECK(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->h_pack), hso_grown(need), hipHostMallocDefault));
+    ctx->h_pack_cap = hso_grown(need);
   }
   ListRec* hr = reinterpret_cast<ListRec*>(ctx->h_pack);
   size_t at = 0;
@@ -518,13 +525,7 @@ extern "C" int hso_gpu_debug_wave_primitives(hso_gpu_ctx* ctx, const double* in,
     return hso_fail(ctx, HSO_E_INVALID, "debug_wave_primitives: n_in / n_out are not the sizes the header states");
   const size_t b_in = (size_t)n_in * sizeof(double), b_out = (size_t)n_out * sizeof(double), need = b_in + b_out;
   HSO_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (ctx->batch_cap < need) {
-    HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_batch) (void)hipFree(ctx->d_batch);
-    ctx->d_batch = nullptr; ctx->batch_cap = 0;
-    HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_batch), hso_grown(need)));
-    ctx->batch_cap = hso_grown(need);
-  }
+  if (int rc = hso_batch_reserve(ctx, need)) return rc;
   double* d_in = reinterpret_cast<double*>(ctx->d_batch);
   double* d_out = reinterpret_cast<double*>(ctx->d_batch + b_in);
   HSO_HIP_CHECK(ctx, hipMemcpyAsync(d_in, in, b_in, hipMemcpyHostToDevice, ctx->stream));
@@ -680,13 +681,7 @@ int hso_gpu_frame_upload_resized(hso_gpu_ctx* ctx, int64_t frame_id, const uint8
   const uint8_t* d_src = img;
   if (!img_is_device) {
     const size_t need = (size_t)src_width * src_height;
-    if (ctx->batch_cap < need) {
-      HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-      if (ctx->d_batch) (void)hipFree(ctx->d_batch);
-      ctx->d_batch = nullptr; ctx->batch_cap = 0;
-      HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_batch), hso_grown(need)));
-      ctx->batch_cap = hso_grown(need);
-    }
+    if (int rc = hso_batch_reserve(ctx, need)) return rc;
     HSO_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_batch, img, need, hipMemcpyHostToDevice, ctx->stream));
     d_src = reinterpret_cast<const uint8_t*>(ctx->d_batch);
   }
@@ -741,15 +736,9 @@ int hso_gpu_frame_upload_batch(hso_gpu_ctx* ctx, const int64_t* frame_ids, const
     fresh.push_back(i);
   }
 #define HSO_BATCH_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { ctx->err = std::string(#expr) + ": " + hipGetErrorString(_e); undo(); return HSO_E_HIP; } } while (0)
-  const size_t b_ptr = ((size_t)n * sizeof(void*) + 255) & ~size_t(255);
+  const size_t b_ptr = hso_al256((size_t)n * sizeof(void*));
   const size_t need = 2 * b_ptr + (size_t)n * sizeof(hso_frame_stats);
-  if (ctx->batch_cap < need) {
-    HSO_BATCH_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->d_batch) (void)hipFree(ctx->d_batch);
-    ctx->d_batch = nullptr; ctx->batch_cap = 0;
-    HSO_BATCH_TRY(hipMalloc(reinterpret_cast<void**>(&ctx->d_batch), hso_grown(need)));
-    ctx->batch_cap = hso_grown(need);
-  }
+  if (int rc = hso_batch_reserve(ctx, need)) { undo(); return rc; }
   uint8_t** d_bases = reinterpret_cast<uint8_t**>(ctx->d_batch);
   const uint8_t** d_srcs = reinterpret_cast<const uint8_t**>(ctx->d_batch + b_ptr);
   hso_frame_stats* d_stats = reinterpret_cast<hso_frame_stats*>(ctx->d_batch + 2 * b_ptr);

@@ -449,7 +449,6 @@ static int detect_candidates_run(hso_gpu_ctx* ctx, const int64_t* frame_ids, int
   // of the kernels below on the same stream.  (The initialisation entry, hso_gpu_detect_candidates_init, reads no gradient image.)
   if (int rc = hso_frame_require_gradients(ctx, frame_ids, n_frames)) return rc;
   const PyrGeom g = it0->second.g;
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
   // extra area: [have flags of every frame | pass flags] (one memset), edgelet totals, then the frame slices
   EdgeArgs& A = run->A;
   A = EdgeArgs{};
@@ -467,10 +466,10 @@ static int detect_candidates_run(hso_gpu_ctx* ctx, const int64_t* frame_ids, int
     // frame store accepts; .at() would throw in the reference otherwise
     if ((L.H - 1) / L.grid * L.gcols + (L.W - 1) / L.grows >= cells)
       return hso_fail(ctx, HSO_E_INVALID, "detect_candidates: grid index out of range for this image size");
-    L.o_have = have_bytes; have_bytes += al((size_t)cells);
-    L.o_map = o; o += al((size_t)L.W * L.H);
-    L.o_res = o; o += al(sizeof(hso_edgelet) * (size_t)cells);
-    L.o_out = o; o += al(sizeof(hso_edgelet) * (size_t)edgelet_cap);
+    L.o_have = have_bytes; have_bytes += hso_al256((size_t)cells);
+    L.o_map = o; o += hso_al256((size_t)L.W * L.H);
+    L.o_res = o; o += hso_al256(sizeof(hso_edgelet) * (size_t)cells);
+    L.o_out = o; o += hso_al256(sizeof(hso_edgelet) * (size_t)edgelet_cap);
     max_cells = cells > max_cells ? cells : max_cells;
     L.tiles_x = (L.W + CLOSE_TW - 1) / CLOSE_TW; L.tiles_y = (L.H + CLOSE_TH - 1) / CLOSE_TH;
     L.tile_base = n_tiles;
@@ -480,15 +479,15 @@ static int detect_candidates_run(hso_gpu_ctx* ctx, const int64_t* frame_ids, int
   }
   // tile tables behind the maps: weak[n_tiles], chg[EDGE_ROUND + 1][n_tiles]
   A.n_tiles = n_tiles;
-  A.o_weak = o; o += al((size_t)n_tiles);
-  A.o_chg = o; o += al((size_t)(EDGE_ROUND + 1) * n_tiles);
+  A.o_weak = o; o += hso_al256((size_t)n_tiles);
+  A.o_chg = o; o += hso_al256((size_t)(EDGE_ROUND + 1) * n_tiles);
   const size_t chg_bytes = (size_t)(EDGE_ROUND + 1) * n_tiles;
   // have flags live per frame in front of the slices: offsets above are relative to a frame's have block
   const size_t have_per_frame = have_bytes;
-  const size_t slice = al(o + have_per_frame);
+  const size_t slice = hso_al256(o + have_per_frame);
   for (int l = 0; l < n_levels; l++) A.lv[l].o_have += o;    // have block sits at the end of each slice
-  const size_t o_flags = 0, o_totals = al(sizeof(int) * (EDGE_ROUND + 1));
-  const size_t o_slices = o_totals + al(sizeof(int) * (size_t)n_frames * n_levels);
+  const size_t o_flags = 0, o_totals = hso_al256(sizeof(int) * (EDGE_ROUND + 1));
+  const size_t o_slices = o_totals + hso_al256(sizeof(int) * (size_t)n_frames * n_levels);
   const size_t extra = o_slices + slice * (size_t)n_frames;
 
   FastPlan& P = run->P;
@@ -695,10 +694,9 @@ extern "C" int hso_gpu_detect_select_multi(hso_gpu_ctx* ctx, const int64_t* fram
     kbeg[(size_t)i + 1] = (int32_t)total;
     most = at > most ? (int)at : most;
   }
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t o_kbeg = 0, o_tab = al(sizeof(int) * kbeg.size()), o_nout = o_tab + al(sizeof(int) * tab.size());
-  const size_t o_occ = o_nout + al(sizeof(int) * (size_t)n_frames), o_keys = o_occ + al(sizeof(float) * 2 * n_occ);
-  const size_t o_out = o_keys + al(sizeof(hso_keypoint) * total), o_scratch = o_out + al(sizeof(hso_keypoint) * (size_t)n_frames * out_cap);
+  const size_t o_kbeg = 0, o_tab = hso_al256(sizeof(int) * kbeg.size()), o_nout = o_tab + hso_al256(sizeof(int) * tab.size());
+  const size_t o_occ = o_nout + hso_al256(sizeof(int) * (size_t)n_frames), o_keys = o_occ + hso_al256(sizeof(float) * 2 * n_occ);
+  const size_t o_out = o_keys + hso_al256(sizeof(hso_keypoint) * total), o_scratch = o_out + hso_al256(sizeof(hso_keypoint) * (size_t)n_frames * out_cap);
   char* d = nullptr;
   if (int rc = hso_octree_reserve(ctx, o_scratch + hso_octree_scratch_bytes(plan, n_frames, total), &d)) return rc;
   HSO_HIP_CHECK(ctx, hipMemcpyAsync(d + o_kbeg, kbeg.data(), sizeof(int) * kbeg.size(), hipMemcpyHostToDevice, ctx->stream));
@@ -801,7 +799,6 @@ extern "C" int hso_gpu_detect_candidates_init(hso_gpu_ctx* ctx, const int64_t* f
   auto it0 = ctx->frames.find(frame_ids[0]);
   if (it0 == ctx->frames.end()) return hso_fail(ctx, HSO_E_NOFRAME, "detect_candidates_init: frame not resident");
   const PyrGeom g = it0->second.g;
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
   EdgeArgs A{};
   size_t o = 0;
   int vw = g.w[0], vh = g.h[0], max_words = 0;
@@ -813,19 +810,19 @@ extern "C" int hso_gpu_detect_candidates_init(hso_gpu_ctx* ctx, const int64_t* f
     vw /= 2; vh /= 2;
     if ((L.H - 1) / L.grid * L.gcols + (L.W - 1) / L.grows >= L.gcols * L.grows)
       return hso_fail(ctx, HSO_E_INVALID, "detect_candidates_init: grid index out of range for this image size");
-    L.o_have = o; o += al((size_t)L.gcols * L.grows);
+    L.o_have = o; o += hso_al256((size_t)L.gcols * L.grows);
   }
   const size_t have_bytes = o;
   const int cells0 = A.lv[0].gcols * A.lv[0].grows;
-  const size_t o_first = o; o += al(sizeof(int) * (size_t)cells0);
-  const size_t o_fout = o; o += al(sizeof(hso_corner) * (size_t)fill_cap);
+  const size_t o_first = o; o += hso_al256(sizeof(int) * (size_t)cells0);
+  const size_t o_fout = o; o += hso_al256(sizeof(hso_corner) * (size_t)fill_cap);
   const size_t slice = o;
   // FAST-12 survivors of level 0: at most one per 2x2 pixels survives a 3x3 non-maximum suppression
   const int cap12 = (g.w[0] / 2 + 1) * (g.h[0] / 2 + 1);
   FastPlan P12;
   const size_t bytes12 = hso_fast_plan(g, n_frames, 1, cap12, &P12);
-  const size_t o_p12 = 0, o_slices = al(bytes12), o_ftot = o_slices + slice * (size_t)n_frames;
-  const size_t extra = o_ftot + al(sizeof(int) * (size_t)n_frames);
+  const size_t o_p12 = 0, o_slices = hso_al256(bytes12), o_ftot = o_slices + slice * (size_t)n_frames;
+  const size_t extra = o_ftot + hso_al256(sizeof(int) * (size_t)n_frames);
 
   FastPlan P;
   const int rc = hso_fast_enqueue(ctx, frame_ids, n_frames, n_levels, min_thresh, 8, corner_cap, extra, &P);

@@ -207,24 +207,23 @@ size_t hso_fast_plan(const PyrGeom& g, int n_frames, int n_levels, int cap, Fast
 {
   FastPlan& P = *plan;
   P.g = g; P.n_frames = n_frames; P.n_levels = n_levels; P.cap = cap;
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
   // slice of one frame: [row counts of all levels | per level: mask, row offsets, corner list]
   size_t o = 0;
   for (int l = 0; l < n_levels; l++) {
     P.wpr[l] = (g.w[l] + FAST_TW - 1) / FAST_TW;
-    P.o_cnt[l] = o; o += al(sizeof(int) * (size_t)g.h[l]);
+    P.o_cnt[l] = o; o += hso_al256(sizeof(int) * (size_t)g.h[l]);
   }
   P.cnt_bytes = o;
   for (int l = 0; l < n_levels; l++) {
-    P.o_mask[l] = o; o += al(sizeof(unsigned long long) * (size_t)g.h[l] * P.wpr[l]);
-    P.o_off[l] = o; o += al(sizeof(int) * (size_t)g.h[l]);
-    P.o_out[l] = o; o += al(sizeof(hso_corner) * (size_t)cap);
+    P.o_mask[l] = o; o += hso_al256(sizeof(unsigned long long) * (size_t)g.h[l] * P.wpr[l]);
+    P.o_off[l] = o; o += hso_al256(sizeof(int) * (size_t)g.h[l]);
+    P.o_out[l] = o; o += hso_al256(sizeof(hso_corner) * (size_t)cap);
   }
   P.per_frame = o;
   P.o_tab = P.per_frame * (size_t)n_frames;
-  P.o_tot = P.o_tab + al(sizeof(void*) * (size_t)n_frames);
-  P.o_thr = P.o_tot + al(sizeof(int) * (size_t)n_frames * n_levels);
-  P.o_extra = P.o_thr + al(sizeof(int) * 3 * (size_t)n_frames);
+  P.o_tot = P.o_tab + hso_al256(sizeof(void*) * (size_t)n_frames);
+  P.o_thr = P.o_tot + hso_al256(sizeof(int) * (size_t)n_frames * n_levels);
+  P.o_extra = P.o_thr + hso_al256(sizeof(int) * 3 * (size_t)n_frames);
   return P.o_extra;
 }
 
@@ -269,14 +268,8 @@ int hso_fast_enqueue(hso_gpu_ctx* ctx, const int64_t* frame_ids, int n_frames, i
     else if (!same_geom(it->second.g, g)) return hso_fail(ctx, HSO_E_INVALID, "fast_detect: frames of one batch must share one size");
     h_bases[i] = it->second.base;
   }
-  const size_t need = hso_fast_plan(g, n_frames, n_levels, cap, &P) + ((extra + 255) & ~size_t(255));
-  if (ctx->batch_cap < need) {
-    HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_batch) (void)hipFree(ctx->d_batch);
-    ctx->d_batch = nullptr; ctx->batch_cap = 0;
-    HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_batch), hso_grown(need)));
-    ctx->batch_cap = hso_grown(need);
-  }
+  const size_t need = hso_fast_plan(g, n_frames, n_levels, cap, &P) + hso_al256(extra);
+  if (int rc = hso_batch_reserve(ctx, need)) return rc;
   char* d = reinterpret_cast<char*>(ctx->d_batch);
   P.d = d;
   HSO_HIP_CHECK(ctx, hipMemcpyAsync(d + P.o_tab, h_bases.data(), sizeof(void*) * (size_t)n_frames, hipMemcpyHostToDevice, ctx->stream));

@@ -578,13 +578,7 @@ extern "C" int hso_gpu_debug_sobel_taps(hso_gpu_ctx* ctx, int64_t frame_id, int 
   const int W = g.w[level], H = g.h[level];
   const size_t plane4 = (size_t)4 * W * H * sizeof(int16_t), need = 2 * plane4;
   HSO_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (ctx->batch_cap < need) {
-    HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_batch) (void)hipFree(ctx->d_batch);
-    ctx->d_batch = nullptr; ctx->batch_cap = 0;
-    HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_batch), hso_grown(need)));
-    ctx->batch_cap = hso_grown(need);
-  }
+  if (int rc = hso_batch_reserve(ctx, need)) return rc;
   int16_t* d_gx = reinterpret_cast<int16_t*>(ctx->d_batch);
   int16_t* d_gy = reinterpret_cast<int16_t*>(ctx->d_batch + plane4);
   hipLaunchKernelGGL(k_debug_sobel_taps, dim3((W * H + 255) / 256), dim3(256), 0, ctx->stream, it->second.base + g.off[level], W, H, d_gx, d_gy);

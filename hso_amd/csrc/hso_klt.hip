@@ -255,18 +255,12 @@ extern "C" int hso_gpu_klt_track(hso_gpu_ctx* ctx, int64_t frame_prev, int64_t f
   size_t off = 0, img_off[2][KLT_MAX_LEVELS], der_off[KLT_MAX_LEVELS];
   L.w[0] = g.w[0]; L.h[0] = g.h[0];
   for (int l = 1; l <= L.last; l++) { L.w[l] = (L.w[l - 1] + 1) / 2; L.h[l] = (L.h[l - 1] + 1) / 2; }
-  auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+  auto take = [&](size_t bytes) { const size_t o = off; off += hso_al256(bytes); return o; };
   for (int f = 0; f < 2; f++) for (int l = 1; l <= L.last; l++) img_off[f][l] = take((size_t)L.w[l] * L.h[l]);
   for (int l = 0; l <= L.last; l++) der_off[l] = take(sizeof(short2) * (size_t)L.w[l] * L.h[l]);
   const size_t o_prev = take(sizeof(float2) * (size_t)n), o_init = take(sizeof(float2) * (size_t)n), o_out = take(sizeof(hso_klt_result) * (size_t)n);
   // the context's grow-only work area (no allocation per call: hipFree synchronises the device)
-  if (ctx->batch_cap < off) {
-    HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_batch) (void)hipFree(ctx->d_batch);
-    ctx->d_batch = nullptr; ctx->batch_cap = 0;
-    HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_batch), hso_grown(off)));
-    ctx->batch_cap = hso_grown(off);
-  }
+  if (int rc = hso_batch_reserve(ctx, off)) return rc;
   char* d = ctx->d_batch;
   int rc = HSO_OK;
   auto body = [&]() -> int {
@@ -314,7 +308,7 @@ extern "C" int hso_gpu_klt_debug_level(hso_gpu_ctx* ctx, int64_t frame, int leve
   w[0] = g.w[0]; h[0] = g.h[0];
   for (int l = 1; l <= level; l++) { w[l] = (w[l - 1] + 1) / 2; h[l] = (h[l - 1] + 1) / 2; }
   uint8_t* d = nullptr;
-  const size_t lvl_bytes = ((size_t)g.w[0] * g.h[0] + 255) & ~(size_t)255;
+  const size_t lvl_bytes = hso_al256((size_t)g.w[0] * g.h[0]);
   if (hipMalloc(&d, 2 * lvl_bytes + sizeof(short2) * (size_t)w[level] * h[level]) != hipSuccess) return hso_fail(ctx, HSO_E_NOMEM, "klt_debug_level");
   const uint8_t* src = it->second.base + g.off[0];
   const dim3 tb(32, 8);

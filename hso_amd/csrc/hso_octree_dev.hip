@@ -273,24 +273,18 @@ int hso_octree_plan(hso_gpu_ctx* ctx, int min_x, int max_x, int min_y, int max_y
   // a sweep runs only while it cannot pass n_features (list + 3 per multi-key child <= n_features), except the first (4 per column);
   // the second phase stops within 3 of n_features
   plan->ncap = std::max(std::max(n_features, 0) + 3, 4 * nIni) + 5;
-  plan->per_set = ((sizeof(OctNode) * 2 + sizeof(int) * 6) * (size_t)plan->ncap + 255) & ~size_t(255);
+  plan->per_set = hso_al256((sizeof(OctNode) * 2 + sizeof(int) * 6) * (size_t)plan->ncap);
   return HSO_OK;
 }
 
 size_t hso_octree_scratch_bytes(const OctreePlan& plan, int n_sets, size_t total_keys)
 {
-  return ((sizeof(int) * total_keys + 255) & ~size_t(255)) + plan.per_set * (size_t)n_sets;
+  return hso_al256(sizeof(int) * total_keys) + plan.per_set * (size_t)n_sets;
 }
 
 int hso_octree_reserve(hso_gpu_ctx* ctx, size_t bytes, char** d)
 {
-  if (ctx->octree_cap < bytes || !ctx->d_octree) {
-    HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_octree) (void)hipFree(ctx->d_octree);
-    ctx->d_octree = nullptr; ctx->octree_cap = 0;
-    HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_octree), hso_grown(bytes)));
-    ctx->octree_cap = hso_grown(bytes);
-  }
+  if (int rc = hso_dev_reserve(ctx, ctx->stream, &ctx->d_octree, &ctx->octree_cap, bytes)) return rc;   // (bytes > 0: both callers' tables are never empty)
   *d = ctx->d_octree;
   return HSO_OK;
 }
@@ -301,7 +295,7 @@ int hso_octree_launch(hso_gpu_ctx* ctx, const OctreePlan& plan, const hso_keypoi
   OctArgs A;
   A.keys = d_keys; A.key_begin = d_key_begin;
   A.node_of = reinterpret_cast<int*>(d_scratch);
-  A.work = d_scratch + ((sizeof(int) * total_keys + 255) & ~size_t(255)); A.per_set = plan.per_set;
+  A.work = d_scratch + hso_al256(sizeof(int) * total_keys); A.per_set = plan.per_set;
   A.ncap = plan.ncap; A.n_ini = plan.n_ini; A.hX = plan.hX;
   A.min_y = plan.min_y; A.max_y = plan.max_y; A.n_features = plan.n_features;
   A.out = d_out; A.out_cap = out_cap; A.n_out = d_n_out;
@@ -326,9 +320,8 @@ extern "C" int hso_gpu_select_octree_batch(hso_gpu_ctx* ctx, const hso_keypoint*
   OctreePlan plan;
   if (int rc = hso_octree_plan(ctx, min_x, max_x, min_y, max_y, n_features, &plan)) return rc;
   HSO_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t o_begin = 0, o_nout = al(sizeof(int) * ((size_t)n_sets + 1)), o_keys = o_nout + al(sizeof(int) * (size_t)n_sets);
-  const size_t o_out = o_keys + al(sizeof(hso_keypoint) * total), o_scratch = o_out + al(sizeof(hso_keypoint) * (size_t)n_sets * out_cap);
+  const size_t o_begin = 0, o_nout = hso_al256(sizeof(int) * ((size_t)n_sets + 1)), o_keys = o_nout + hso_al256(sizeof(int) * (size_t)n_sets);
+  const size_t o_out = o_keys + hso_al256(sizeof(hso_keypoint) * total), o_scratch = o_out + hso_al256(sizeof(hso_keypoint) * (size_t)n_sets * out_cap);
   char* d = nullptr;
   if (int rc = hso_octree_reserve(ctx, o_scratch + hso_octree_scratch_bytes(plan, n_sets, total), &d)) return rc;
   HSO_HIP_CHECK(ctx, hipMemcpyAsync(d + o_begin, key_begin, sizeof(int) * ((size_t)n_sets + 1), hipMemcpyHostToDevice, ctx->stream));

@@ -649,20 +649,13 @@ extern "C" int hso_gpu_pose_optimize_batch(hso_gpu_ctx* ctx, const hso_camera* c
     }
     tot_feats += jobs[j].n_feats; tot_poses += jobs[j].n_poses;
   }
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t o_feats = al(sizeof(PoseJobDev) * n_jobs);
-  const size_t o_poses = o_feats + al(sizeof(hso_pose_feat) * tot_feats);
-  const size_t o_mask = o_poses + al(sizeof(hso_se3) * tot_poses);
-  const size_t o_res = o_mask + al(tot_feats);
+  const size_t o_feats = hso_al256(sizeof(PoseJobDev) * n_jobs);
+  const size_t o_poses = o_feats + hso_al256(sizeof(hso_pose_feat) * tot_feats);
+  const size_t o_mask = o_poses + hso_al256(sizeof(hso_se3) * tot_poses);
+  const size_t o_res = o_mask + hso_al256(tot_feats);
   const size_t need = o_res + sizeof(hso_pose_result) * n_jobs;
   // device work area and pinned host staging are the context's grow-only buffers: no allocation per call
-  if (ctx->batch_cap < need) {
-    HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_batch) (void)hipFree(ctx->d_batch);
-    ctx->d_batch = nullptr; ctx->batch_cap = 0;
-    HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_batch), hso_grown(need)));
-    ctx->batch_cap = hso_grown(need);
-  }
+  if (int rc = hso_batch_reserve(ctx, need)) return rc;
   char* d = ctx->d_batch;
   char* h = hso_pinned(ctx, 0, o_res);
   char* hm = hso_pinned(ctx, 1, tot_feats + sizeof(hso_pose_result) * n_jobs + 64);

@@ -886,17 +886,10 @@ static __global__ __launch_bounds__(256) void k_seed_post(SeedConsts C, SeedDev*
 static int seed_observe_launch_on(hso_gpu_ctx* ctx, hipStream_t stream, char** scratch, size_t* scratch_cap, const SeedConsts& C, SeedDev* seeds, int n,
                                   hso_seed_out* outs)
 {
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t need = al((size_t)n * sizeof(SeedPre)) + al((size_t)n * sizeof(SeedMid));
-  if (*scratch_cap < need) {
-    HSO_HIP_CHECK(ctx, hipStreamSynchronize(stream));
-    if (*scratch) (void)hipFree(*scratch);
-    *scratch = nullptr; *scratch_cap = 0;
-    HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(scratch), hso_grown(need)));
-    *scratch_cap = hso_grown(need);
-  }
+  const size_t need = hso_al256((size_t)n * sizeof(SeedPre)) + hso_al256((size_t)n * sizeof(SeedMid));
+  if (int rc = hso_dev_reserve(ctx, stream, scratch, scratch_cap, need)) return rc;
   SeedPre* pre = reinterpret_cast<SeedPre*>(*scratch);
-  SeedMid* mid = reinterpret_cast<SeedMid*>(*scratch + al((size_t)n * sizeof(SeedPre)));
+  SeedMid* mid = reinterpret_cast<SeedMid*>(*scratch + hso_al256((size_t)n * sizeof(SeedPre)));
   const int per_block = 8 * SEED_WAVES_PER_BLOCK;
   hipLaunchKernelGGL(k_seed_pre, dim3((n + 255) / 256), dim3(256), 0, stream, C, seeds, n, pre);
   if (C.frame_keys) hipLaunchKernelGGL(k_seed_image<true>, dim3((n + per_block - 1) / per_block), dim3(64 * SEED_WAVES_PER_BLOCK), 0, stream, C, seeds, n, pre, mid);
@@ -960,16 +953,9 @@ extern "C" int hso_gpu_seed_observe_multi(hso_gpu_ctx* ctx, const hso_camera* ca
     h[i].frame = seed_frame[i]; h[i].pad_ = 0;
     h[i].s = seeds[i];
   }
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t b_in = al((size_t)n_seeds * sizeof(SeedDev)), b_out = al((size_t)n_seeds * sizeof(hso_seed_out));
-  const size_t need = b_in + b_out + al((size_t)n_frames * sizeof(SeedFrameDev));
-  if (ctx->batch_cap < need) {
-    HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_batch) (void)hipFree(ctx->d_batch);
-    ctx->d_batch = nullptr; ctx->batch_cap = 0;
-    HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_batch), hso_grown(need)));
-    ctx->batch_cap = hso_grown(need);
-  }
+  const size_t b_in = hso_al256((size_t)n_seeds * sizeof(SeedDev)), b_out = hso_al256((size_t)n_seeds * sizeof(hso_seed_out));
+  const size_t need = b_in + b_out + hso_al256((size_t)n_frames * sizeof(SeedFrameDev));
+  if (int rc = hso_batch_reserve(ctx, need)) return rc;
   SeedDev* d_in = reinterpret_cast<SeedDev*>(ctx->d_batch);
   hso_seed_out* d_out = reinterpret_cast<hso_seed_out*>(ctx->d_batch + b_in);
   SeedFrameDev* d_fr = reinterpret_cast<SeedFrameDev*>(ctx->d_batch + b_in + b_out);
@@ -1067,20 +1053,7 @@ int hso_seed_table_rows(hso_gpu_ctx* ctx, int table, const int32_t* slots, int n
 
 template <typename T> static int grow_dev(hso_gpu_ctx* ctx, T** p, size_t* cap, size_t need, size_t keep)
 {
-  if (*cap >= need) return HSO_OK;
-  const size_t ncap = std::max(need, *cap * 2 + 1024);
-  T* q = nullptr;
-  HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&q), ncap * sizeof(T)));
-  if (*p && keep) {
-    hipError_t e = hipMemcpyAsync(q, *p, keep * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { (void)hipFree(q); ctx->err = hipGetErrorString(e); return HSO_E_HIP; }
-  } else if (*p) {
-    HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  if (*p) (void)hipFree(*p);
-  *p = q; *cap = ncap;
-  return HSO_OK;
+  return hso_dev_grow_keep(ctx, p, cap, need, keep, std::max(need, *cap * 2 + 1024));
 }
 
 extern "C" {
@@ -1163,13 +1136,7 @@ int hso_gpu_seed_table_erase(hso_gpu_ctx* ctx, int table, const int32_t* slots, 
   // copies per step of 64 sequences: 3 ms of copy kernels and as much enqueue time)
   HSO_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const size_t need = sizeof(int32_t) * dead.size();
-  if (ctx->batch_cap < need) {
-    HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_batch) (void)hipFree(ctx->d_batch);
-    ctx->d_batch = nullptr; ctx->batch_cap = 0;
-    HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_batch), hso_grown(need)));
-    ctx->batch_cap = hso_grown(need);
-  }
+  if (int rc = hso_batch_reserve(ctx, need)) return rc;
   HSO_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_batch, dead.data(), need, hipMemcpyHostToDevice, ctx->stream));
   hipLaunchKernelGGL(k_seed_mark_dead, dim3((unsigned)((dead.size() + 255) / 256)), dim3(256), 0, ctx->stream, t->d, reinterpret_cast<const int32_t*>(ctx->d_batch),
                      (int)dead.size());
@@ -1380,7 +1347,7 @@ int hso_gpu_seed_table_observe_previous(hso_gpu_ctx* ctx, const hso_camera* cam,
   if (!t || !cam || n < 0 || (n > 0 && (!host_frame_ids || !pre_frames))) return hso_fail(ctx, HSO_E_INVALID, "seed_table_observe_previous: bad argument");
   if (t->n == 0) return HSO_OK;
   HSO_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const size_t b_fr = ((size_t)std::max(n, 1) * sizeof(SeedFrameDev) + 255) & ~size_t(255);
+  const size_t b_fr = hso_al256((size_t)std::max(n, 1) * sizeof(SeedFrameDev));
   char* stage = reinterpret_cast<char*>(hso_pinned(ctx, 0, b_fr + (size_t)std::max(n, 1) * sizeof(int64_t)));
   if (!stage) return HSO_E_NOMEM;
   if (int rc = seed_previous_stage(ctx, t, cam, host_frame_ids, pre_frames, n, stage, b_fr)) return rc;
@@ -1424,8 +1391,8 @@ int hso_gpu_seed_table_observe_previous_begin(hso_gpu_ctx* ctx, const hso_camera
   ctx->seed_inflight_table = table; ctx->seed_inflight_n = t->n;
   if (t->n == 0) { ctx->seed_inflight = true; return HSO_OK; }   // nothing to launch; _end reports nothing
   // page-locked staging of its own (the context's slots are reused by the calls that overlap this pass): [frames | keys | briefs]
-  const size_t b_fr = ((size_t)std::max(n, 1) * sizeof(SeedFrameDev) + 255) & ~size_t(255);
-  const size_t b_key = ((size_t)std::max(n, 1) * sizeof(int64_t) + 255) & ~size_t(255);
+  const size_t b_fr = hso_al256((size_t)std::max(n, 1) * sizeof(SeedFrameDev));
+  const size_t b_key = hso_al256((size_t)std::max(n, 1) * sizeof(int64_t));
   const size_t need = b_fr + b_key + t->n * sizeof(hso_seed_brief);
   if (ctx->h_seed_pin_cap < need) {
     if (ctx->h_seed_pin) (void)hipHostFree(ctx->h_seed_pin);
@@ -1492,15 +1459,8 @@ int hso_gpu_seed_table_set_host_pose(hso_gpu_ctx* ctx, int table, const int64_t*
   if (!t || n < 0 || (n > 0 && (!frame_ids || !T_f_w))) return hso_fail(ctx, HSO_E_INVALID, "seed_table_set_host_pose: bad argument");
   if (n == 0 || t->n == 0) return HSO_OK;
   HSO_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t b_id = al(sizeof(int64_t) * (size_t)n), need = b_id + al(sizeof(hso_se3) * (size_t)n);
-  if (ctx->batch_cap < need) {
-    HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_batch) (void)hipFree(ctx->d_batch);
-    ctx->d_batch = nullptr; ctx->batch_cap = 0;
-    HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_batch), hso_grown(need)));
-    ctx->batch_cap = hso_grown(need);
-  }
+  const size_t b_id = hso_al256(sizeof(int64_t) * (size_t)n), need = b_id + hso_al256(sizeof(hso_se3) * (size_t)n);
+  if (int rc = hso_batch_reserve(ctx, need)) return rc;
   HSO_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_batch, frame_ids, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   HSO_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_batch + b_id, T_f_w, sizeof(hso_se3) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   hipLaunchKernelGGL(k_seed_set_host_pose, dim3((unsigned)((t->n + 255) / 256)), dim3(256), 0, ctx->stream, t->d, (int)t->n,

@@ -270,29 +270,22 @@ extern "C" int hso_gpu_reproject_select(hso_gpu_ctx* ctx, const int32_t* frame_b
     }
   }
   HSO_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
   // inputs | frame records | per-frame scratch | outputs
   size_t o = 0;
-  const size_t o_cell = o; o += al(sizeof(int32_t) * (size_t)n_total);
-  const size_t o_q = o; o += al((size_t)n_total);
-  const size_t o_f = o; o += al((size_t)n_total);
-  const size_t o_ord = o; o += al(sizeof(int32_t) * (size_t)n_cells);
-  const size_t o_fr = o; o += al(sizeof(SelFrame) * (size_t)n_frames);
+  const size_t o_cell = o; o += hso_al256(sizeof(int32_t) * (size_t)n_total);
+  const size_t o_q = o; o += hso_al256((size_t)n_total);
+  const size_t o_f = o; o += hso_al256((size_t)n_total);
+  const size_t o_ord = o; o += hso_al256(sizeof(int32_t) * (size_t)n_cells);
+  const size_t o_fr = o; o += hso_al256(sizeof(SelFrame) * (size_t)n_frames);
   const size_t in_bytes = o;
-  const size_t o_out = o; o += al(sizeof(int32_t) * (size_t)std::max(n_total, 1));
-  const size_t o_cnt = o; o += al(sizeof(int32_t) * 4 * (size_t)n_frames);
-  const size_t o_list = o; o += al(sizeof(int32_t) * (size_t)std::max(n_total, 1));
-  const size_t per_frame = al(sizeof(int32_t) * (size_t)(n_cells + 1)) + 4 * al(sizeof(int32_t) * (size_t)n_cells) + al(sizeof(int32_t) * 3 * (size_t)n_cells);
+  const size_t o_out = o; o += hso_al256(sizeof(int32_t) * (size_t)std::max(n_total, 1));
+  const size_t o_cnt = o; o += hso_al256(sizeof(int32_t) * 4 * (size_t)n_frames);
+  const size_t o_list = o; o += hso_al256(sizeof(int32_t) * (size_t)std::max(n_total, 1));
+  const size_t per_frame = hso_al256(sizeof(int32_t) * (size_t)(n_cells + 1)) + 4 * hso_al256(sizeof(int32_t) * (size_t)n_cells) + hso_al256(sizeof(int32_t) * 3 * (size_t)n_cells);
   // the scan array also serves reprojectCellAll (indexed by candidate): n < max_fts + 50 entries
-  const size_t scan_bytes = al(sizeof(int32_t) * (size_t)std::max(n_cells, max_fts + 50));
+  const size_t scan_bytes = hso_al256(sizeof(int32_t) * (size_t)std::max(n_cells, max_fts + 50));
   const size_t o_scr = o; o += (per_frame + scan_bytes) * (size_t)n_frames;
-  if (ctx->batch_cap < o) {
-    HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_batch) (void)hipFree(ctx->d_batch);
-    ctx->d_batch = nullptr; ctx->batch_cap = 0;
-    HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_batch), hso_grown(o)));
-    ctx->batch_cap = hso_grown(o);
-  }
+  if (int rc = hso_batch_reserve(ctx, o)) return rc;
   char* d = ctx->d_batch;
   char* h = hso_pinned(ctx, 0, in_bytes);
   if (!h) return HSO_E_NOMEM;
@@ -305,12 +298,12 @@ extern "C" int hso_gpu_reproject_select(hso_gpu_ctx* ctx, const int32_t* frame_b
     char* s = d + o_scr + (per_frame + scan_bytes) * (size_t)f;
     SelFrame& F = hf[f];
     F.first = frame_begin[f]; F.n = frame_begin[f + 1] - frame_begin[f]; F.n_dev = nullptr;
-    F.cnt = reinterpret_cast<int*>(s); s += al(sizeof(int32_t) * (size_t)(n_cells + 1));
-    F.fill = reinterpret_cast<int*>(s); s += al(sizeof(int32_t) * (size_t)n_cells);
-    F.e1 = reinterpret_cast<int*>(s); s += al(sizeof(int32_t) * (size_t)n_cells);
-    F.e2 = reinterpret_cast<int*>(s); s += al(sizeof(int32_t) * (size_t)n_cells);
-    F.a3 = reinterpret_cast<int*>(s); s += al(sizeof(int32_t) * (size_t)n_cells);
-    F.p3 = reinterpret_cast<int*>(s); s += al(sizeof(int32_t) * 3 * (size_t)n_cells);
+    F.cnt = reinterpret_cast<int*>(s); s += hso_al256(sizeof(int32_t) * (size_t)(n_cells + 1));
+    F.fill = reinterpret_cast<int*>(s); s += hso_al256(sizeof(int32_t) * (size_t)n_cells);
+    F.e1 = reinterpret_cast<int*>(s); s += hso_al256(sizeof(int32_t) * (size_t)n_cells);
+    F.e2 = reinterpret_cast<int*>(s); s += hso_al256(sizeof(int32_t) * (size_t)n_cells);
+    F.a3 = reinterpret_cast<int*>(s); s += hso_al256(sizeof(int32_t) * (size_t)n_cells);
+    F.p3 = reinterpret_cast<int*>(s); s += hso_al256(sizeof(int32_t) * 3 * (size_t)n_cells);
     F.scan = reinterpret_cast<int*>(s);
     F.list = reinterpret_cast<int*>(d + o_list) + F.first;
     F.out = reinterpret_cast<int*>(d + o_out) + F.first;
@@ -795,7 +788,6 @@ extern "C" int hso_gpu_seq_chain(hso_gpu_ctx* ctx, const hso_camera* cam, const 
   }
   HSO_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const int n_cells = cfg->n_cells, max_fts = cfg->max_fts, feat_cap = max_fts;
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
   // ---- per job: frames, the map's view, the list slice (as long as the list can get: every point row once, or every feature of
   // max_kfs + 5 keyframes plus candidates and temporary points, whichever is smaller)
   if (int rc = hso_seqmap_flush_kfs(ctx)) return rc;
@@ -844,56 +836,50 @@ extern "C" int hso_gpu_seq_chain(hso_gpu_ctx* ctx, const hso_camera* cam, const 
   const size_t total_kfs = (size_t)kf_begin[(size_t)n_jobs];
   const size_t nt = std::max(total, (size_t)1);
   // ---- the work area
-  const size_t per_frame = al(sizeof(int32_t) * (size_t)(n_cells + 1)) + 4 * al(sizeof(int32_t) * (size_t)n_cells) + al(sizeof(int32_t) * 3 * (size_t)n_cells) +
-                           al(sizeof(int32_t) * (size_t)std::max(n_cells, max_fts + 50));
+  const size_t per_frame = hso_al256(sizeof(int32_t) * (size_t)(n_cells + 1)) + 4 * hso_al256(sizeof(int32_t) * (size_t)n_cells) + hso_al256(sizeof(int32_t) * 3 * (size_t)n_cells) +
+                           hso_al256(sizeof(int32_t) * (size_t)std::max(n_cells, max_fts + 50));
   size_t o = 0;
   // uploaded image: [jobs | list lengths | temps | cell order | selection frames | pose jobs]
-  const size_t o_jobs = o; o += al(sizeof(ChainJobDev) * (size_t)n_jobs);
-  const size_t o_nfts = o; o += al(sizeof(int32_t) * std::max(total_kfs, (size_t)1));
-  const size_t o_temps = o; o += al(sizeof(int32_t) * (size_t)std::max(n_temps_total, 1));
-  const size_t o_order = o; o += al(sizeof(int32_t) * (size_t)n_cells);
-  const size_t o_frames = o; o += al(sizeof(SelFrame) * (size_t)n_jobs);
-  const size_t o_pj = o; o += al(sizeof(PoseJobDev) * (size_t)n_jobs);
-  const size_t o_slices = o; o += al(sizeof(int32_t) * ((size_t)n_jobs + 1));
+  const size_t o_jobs = o; o += hso_al256(sizeof(ChainJobDev) * (size_t)n_jobs);
+  const size_t o_nfts = o; o += hso_al256(sizeof(int32_t) * std::max(total_kfs, (size_t)1));
+  const size_t o_temps = o; o += hso_al256(sizeof(int32_t) * (size_t)std::max(n_temps_total, 1));
+  const size_t o_order = o; o += hso_al256(sizeof(int32_t) * (size_t)n_cells);
+  const size_t o_frames = o; o += hso_al256(sizeof(SelFrame) * (size_t)n_jobs);
+  const size_t o_pj = o; o += hso_al256(sizeof(PoseJobDev) * (size_t)n_jobs);
+  const size_t o_slices = o; o += hso_al256(sizeof(int32_t) * ((size_t)n_jobs + 1));
   const size_t in_bytes = o;
-  const size_t o_cur = o; o += al(sizeof(ChainCur) * (size_t)n_jobs);
-  const size_t o_table = o; o += al(sizeof(double) * std::max(table_doubles, (size_t)1));
-  const size_t o_kfs = o; o += al(hso_chain_sizeof_reproj_kf() * std::max(total_kfs, (size_t)1));
-  const size_t o_ids = o; o += al(sizeof(int32_t) * nt);
-  const size_t o_lq = o; o += al(nt);
-  const size_t o_align = o; o += al(hso_chain_sizeof_align_job() * nt);
-  const size_t o_match = o; o += al(sizeof(hso_align_out) * nt);
-  const size_t o_proj = o; o += al(sizeof(hso_reproj_point) * nt);
-  const size_t o_brief = o; o += al(sizeof(hso_match_brief) * nt);
-  const size_t o_cell = o; o += al(sizeof(int32_t) * nt);
-  const size_t o_q = o; o += al(nt);
-  const size_t o_f = o; o += al(nt);
-  const size_t o_pt = o; o += al(sizeof(int32_t) * nt);
-  const size_t o_ncand = o; o += al(sizeof(int) * (size_t)n_jobs);
-  const size_t o_list = o; o += al(sizeof(int32_t) * nt);
-  const size_t o_exam = o; o += al(sizeof(int32_t) * nt);
-  const size_t o_counts = o; o += al(sizeof(int32_t) * 4 * (size_t)n_jobs);
-  const size_t o_offs = o; o += al(sizeof(int) * (size_t)(n_jobs + 1));
-  const size_t o_out = o; o += al(sizeof(hso_match_brief) * nt);
-  const size_t o_flag = o; o += al(nt);
-  const size_t o_rec = o; o += al(sizeof(hso_frame_match) * nt);
-  const size_t o_ev = o; o += al(sizeof(int32_t) * nt);
+  const size_t o_cur = o; o += hso_al256(sizeof(ChainCur) * (size_t)n_jobs);
+  const size_t o_table = o; o += hso_al256(sizeof(double) * std::max(table_doubles, (size_t)1));
+  const size_t o_kfs = o; o += hso_al256(hso_chain_sizeof_reproj_kf() * std::max(total_kfs, (size_t)1));
+  const size_t o_ids = o; o += hso_al256(sizeof(int32_t) * nt);
+  const size_t o_lq = o; o += hso_al256(nt);
+  const size_t o_align = o; o += hso_al256(hso_chain_sizeof_align_job() * nt);
+  const size_t o_match = o; o += hso_al256(sizeof(hso_align_out) * nt);
+  const size_t o_proj = o; o += hso_al256(sizeof(hso_reproj_point) * nt);
+  const size_t o_brief = o; o += hso_al256(sizeof(hso_match_brief) * nt);
+  const size_t o_cell = o; o += hso_al256(sizeof(int32_t) * nt);
+  const size_t o_q = o; o += hso_al256(nt);
+  const size_t o_f = o; o += hso_al256(nt);
+  const size_t o_pt = o; o += hso_al256(sizeof(int32_t) * nt);
+  const size_t o_ncand = o; o += hso_al256(sizeof(int) * (size_t)n_jobs);
+  const size_t o_list = o; o += hso_al256(sizeof(int32_t) * nt);
+  const size_t o_exam = o; o += hso_al256(sizeof(int32_t) * nt);
+  const size_t o_counts = o; o += hso_al256(sizeof(int32_t) * 4 * (size_t)n_jobs);
+  const size_t o_offs = o; o += hso_al256(sizeof(int) * (size_t)(n_jobs + 1));
+  const size_t o_out = o; o += hso_al256(sizeof(hso_match_brief) * nt);
+  const size_t o_flag = o; o += hso_al256(nt);
+  const size_t o_rec = o; o += hso_al256(sizeof(hso_frame_match) * nt);
+  const size_t o_ev = o; o += hso_al256(sizeof(int32_t) * nt);
   const size_t o_scr = o; o += per_frame * (size_t)n_jobs;
-  const size_t o_pf = o; o += al(sizeof(hso_pose_feat) * (size_t)n_jobs * feat_cap);
-  const size_t o_pp = o; o += al(sizeof(hso_se3) * (size_t)n_jobs * HSO_POSE_MAX_POSES);
-  const size_t o_pnp = o; o += al(sizeof(int) * (size_t)n_jobs);
-  const size_t o_pr = o; o += al(sizeof(hso_pose_result) * (size_t)n_jobs);
-  const size_t o_pk = o; o += al((size_t)n_jobs * feat_cap);
-  const size_t o_pn = o; o += al(sizeof(int) * (size_t)n_jobs);
-  const size_t o_res = o; o += al(sizeof(hso_seq_result) * (size_t)n_jobs);
+  const size_t o_pf = o; o += hso_al256(sizeof(hso_pose_feat) * (size_t)n_jobs * feat_cap);
+  const size_t o_pp = o; o += hso_al256(sizeof(hso_se3) * (size_t)n_jobs * HSO_POSE_MAX_POSES);
+  const size_t o_pnp = o; o += hso_al256(sizeof(int) * (size_t)n_jobs);
+  const size_t o_pr = o; o += hso_al256(sizeof(hso_pose_result) * (size_t)n_jobs);
+  const size_t o_pk = o; o += hso_al256((size_t)n_jobs * feat_cap);
+  const size_t o_pn = o; o += hso_al256(sizeof(int) * (size_t)n_jobs);
+  const size_t o_res = o; o += hso_al256(sizeof(hso_seq_result) * (size_t)n_jobs);
   const size_t need = o;
-  if (ctx->batch_cap < need) {
-    HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_batch) (void)hipFree(ctx->d_batch);
-    ctx->d_batch = nullptr; ctx->batch_cap = 0;
-    HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_batch), hso_grown(need)));
-    ctx->batch_cap = hso_grown(need);
-  }
+  if (int rc = hso_batch_reserve(ctx, need)) return rc;
   char* d = ctx->d_batch;
   // ---- one staging image for everything the kernels read from the caller
   char* h = hso_pinned(ctx, 1, in_bytes);
@@ -915,12 +901,12 @@ extern "C" int hso_gpu_seq_chain(hso_gpu_ctx* ctx, const hso_camera* cam, const 
       char* sc = d + o_scr + per_frame * (size_t)c;
       SelFrame& F = hf[c];
       F.first = hj[(size_t)c].slice_begin; F.n = 0; F.n_dev = reinterpret_cast<const int*>(d + o_ncand) + c;
-      F.cnt = reinterpret_cast<int*>(sc); sc += al(sizeof(int32_t) * (size_t)(n_cells + 1));
-      F.fill = reinterpret_cast<int*>(sc); sc += al(sizeof(int32_t) * (size_t)n_cells);
-      F.e1 = reinterpret_cast<int*>(sc); sc += al(sizeof(int32_t) * (size_t)n_cells);
-      F.e2 = reinterpret_cast<int*>(sc); sc += al(sizeof(int32_t) * (size_t)n_cells);
-      F.a3 = reinterpret_cast<int*>(sc); sc += al(sizeof(int32_t) * (size_t)n_cells);
-      F.p3 = reinterpret_cast<int*>(sc); sc += al(sizeof(int32_t) * 3 * (size_t)n_cells);
+      F.cnt = reinterpret_cast<int*>(sc); sc += hso_al256(sizeof(int32_t) * (size_t)(n_cells + 1));
+      F.fill = reinterpret_cast<int*>(sc); sc += hso_al256(sizeof(int32_t) * (size_t)n_cells);
+      F.e1 = reinterpret_cast<int*>(sc); sc += hso_al256(sizeof(int32_t) * (size_t)n_cells);
+      F.e2 = reinterpret_cast<int*>(sc); sc += hso_al256(sizeof(int32_t) * (size_t)n_cells);
+      F.a3 = reinterpret_cast<int*>(sc); sc += hso_al256(sizeof(int32_t) * (size_t)n_cells);
+      F.p3 = reinterpret_cast<int*>(sc); sc += hso_al256(sizeof(int32_t) * 3 * (size_t)n_cells);
       F.scan = reinterpret_cast<int*>(sc);
       F.list = reinterpret_cast<int*>(d + o_list) + F.first;
       F.out = reinterpret_cast<int*>(d + o_exam) + F.first;

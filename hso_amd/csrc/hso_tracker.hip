@@ -171,12 +171,12 @@ void hso_track_state_free(hso_gpu_ctx* ctx)
 template <typename T>
 static int grow(hso_gpu_ctx* ctx, T** p, size_t* cap, size_t need_bytes)
 {
-  if (*cap >= need_bytes && *p) return HSO_OK;
-  if (*p) { HSO_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(*p); *p = nullptr; }
   const size_t bytes = std::max<size_t>(need_bytes + need_bytes / 4, 256);   // headroom: feature tables vary a little from call to call
-  HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(p), bytes));
-  *cap = bytes;
-  return HSO_OK;
+  char* q = reinterpret_cast<char*>(*p);
+  // a buffer that does not exist yet is allocated even when need_bytes == 0: no caller ever holds a null pointer
+  const int rc = hso_dev_reserve(ctx, ctx->stream, &q, cap, q ? need_bytes : std::max<size_t>(need_bytes, 1), bytes);
+  *p = reinterpret_cast<T*>(q);
+  return rc;
 }
 
 
@@ -604,7 +604,7 @@ int hso_gpu_make_depth_ref(hso_gpu_ctx* ctx, const hso_depth_ref_in* in, int n, 
   HSO_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   char* d = nullptr;
   const size_t b_in = sizeof(hso_depth_ref_in) * n, b_p = sizeof(hso_se3) * n_poses, b_o = sizeof(double) * n;
-  const size_t o1 = (b_in + 255) & ~size_t(255), o2 = o1 + ((b_p + 255) & ~size_t(255));
+  const size_t o1 = hso_al256(b_in), o2 = o1 + hso_al256(b_p);
   HSO_HIP_CHECK(ctx, hipMalloc(reinterpret_cast<void**>(&d), o2 + b_o));
   (void)hipMemcpyAsync(d, in, b_in, hipMemcpyHostToDevice, ctx->stream);
   (void)hipMemcpyAsync(d + o1, poses_f_w, b_p, hipMemcpyHostToDevice, ctx->stream);
