@@ -318,6 +318,14 @@ def load():
     lib.hso_gpu_frame_upload.argtypes = [vp, i64, vp, i32, i32, i32, P(FrameStats)]
     lib.hso_gpu_frame_upload_resized.argtypes = [vp, i64, vp, i32, i32, i32, i32, i32, P(FrameStats)]
     lib.hso_gpu_frame_upload_batch.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
+    lib.hso_gpu_rectify_build_map.argtypes = [P(Camera), vp, vp]
+    lib.hso_gpu_rectify_host.argtypes = [vp, vp, i32, i32, vp, vp]
+    lib.hso_gpu_rectify_map_create.argtypes = [vp, P(Camera), P(C.c_int32)]
+    lib.hso_gpu_rectify_map_create_tables.argtypes = [vp, i32, i32, vp, vp, P(C.c_int32)]
+    lib.hso_gpu_rectify_map_destroy.argtypes = [vp, C.c_int32]
+    lib.hso_gpu_rectify_map_read.argtypes = [vp, C.c_int32, vp, vp]
+    lib.hso_gpu_frame_upload_rectified.argtypes = [vp, i64, vp, i32, i32, C.c_int32, i32, P(FrameStats)]
+    lib.hso_gpu_frame_upload_batch_rectified.argtypes = [vp, vp, vp, i32, C.c_int32, i32, vp]
     lib.hso_gpu_frame_release.argtypes = [vp, i64]
     lib.hso_gpu_frame_release_batch.argtypes = [vp, vp, i32]
     lib.hso_gpu_frame_download_level.argtypes = [vp, i64, i32, vp, P(i32), P(i32)]
@@ -412,13 +420,15 @@ EXPORTED_SYMBOLS = [
     "hso_gpu_seed_table_observe_groups", "hso_gpu_seed_table_set_host_pose",
     "hso_gpu_seed_table_observe_previous", "hso_gpu_seed_table_observe_previous_begin", "hso_gpu_seed_table_observe_previous_end",
     "hso_gpu_select_octree_batch", "hso_gpu_detect_select_multi",
+    "hso_gpu_rectify_build_map", "hso_gpu_rectify_host", "hso_gpu_rectify_map_create", "hso_gpu_rectify_map_create_tables",
+    "hso_gpu_rectify_map_destroy", "hso_gpu_frame_upload_rectified", "hso_gpu_frame_upload_batch_rectified",
 ]
 
 
 # ... and every symbol include/hso_gpu_debug.h declares (parity / trace read-backs, developer probes: not part of the boundary)
 DEBUG_SYMBOLS = ["hso_gpu_debug_census", "hso_gpu_klt_debug_level", "hso_gpu_seq_debug_list", "hso_gpu_seq_debug_ref_table", "hso_gpu_debug_fetch",
                  "hso_gpu_seqmap_debug_dump", "hso_gpu_seq_ba_debug_window", "hso_gpu_debug_sobel_taps", "hso_gpu_debug_frame_stats",
-                 "hso_gpu_debug_wave_primitives"]
+                 "hso_gpu_debug_wave_primitives", "hso_gpu_rectify_map_read"]
 
 
 def select_octree(keys, width, height, n_features):
@@ -434,6 +444,31 @@ def select_octree(keys, width, height, n_features):
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def rectify_build_map(cam):
+    """hso_gpu_rectify_build_map: the camera's fixed-point rectification maps (getRemap + cv::convertMaps) ->
+    (xy int16 [h, w, 2], frac uint16 [h, w]).  Host code: no device needed."""
+    xy = np.zeros((cam.height, cam.width, 2), np.int16)
+    frac = np.zeros((cam.height, cam.width), np.uint16)
+    rc = load().hso_gpu_rectify_build_map(C.byref(cam), _ptr(xy), _ptr(frac))
+    if rc < 0:
+        raise HsoGpuError("rectify_build_map: status %d (the reference rectifies FOV cameras with undistort = true and Equidistant cameras only)" % rc)
+    return xy, frac
+
+
+def rectify_host(xy, frac, img):
+    """hso_gpu_rectify_host: cv::remap(img, ., xy, frac, INTER_LINEAR) with a zero border, on the host -> the rectified image"""
+    xy = np.ascontiguousarray(xy, np.int16)
+    frac = np.ascontiguousarray(frac, np.uint16)
+    img = np.ascontiguousarray(img, np.uint8)
+    h, w = frac.shape
+    assert img.shape == (h, w) and xy.shape == (h, w, 2)
+    out = np.empty((h, w), np.uint8)
+    rc = load().hso_gpu_rectify_host(_ptr(xy), _ptr(frac), w, h, _ptr(img), _ptr(out))
+    if rc < 0:
+        raise HsoGpuError("rectify_host: status %d" % rc)
+    return out
 
 
 class Context:
@@ -561,6 +596,58 @@ class Context:
         rc = self.lib.hso_gpu_frame_upload_batch(self.h, _ptr(ids), _ptr(ptrs), n, width, height, is_dev,
                                                  C.cast(stats, C.c_void_p) if want_stats else None)
         self._check(rc, "frame_upload_batch")
+        return list(stats) if want_stats else None
+
+    # -- rectification
+    def rectify_map_create(self, cam=None, xy=None, frac=None):
+        """A camera's rectification maps on the device (cam), or a caller's own fixed-point maps (xy [h, w, 2] int16, frac [h, w] uint16)
+        -> map id"""
+        out = C.c_int32(-1)
+        if cam is not None:
+            self._check(self.lib.hso_gpu_rectify_map_create(self.h, C.byref(cam), C.byref(out)), "rectify_map_create")
+        else:
+            xy = np.ascontiguousarray(xy, np.int16)
+            frac = np.ascontiguousarray(frac, np.uint16)
+            h, w = frac.shape
+            assert xy.shape == (h, w, 2)
+            self._check(self.lib.hso_gpu_rectify_map_create_tables(self.h, w, h, _ptr(xy), _ptr(frac), C.byref(out)), "rectify_map_create_tables")
+        return out.value
+
+    def rectify_map_destroy(self, map_id):
+        self._check(self.lib.hso_gpu_rectify_map_destroy(self.h, int(map_id)), "rectify_map_destroy")
+
+    def rectify_map_read(self, map_id, width, height):
+        xy = np.zeros((height, width, 2), np.int16)
+        frac = np.zeros((height, width), np.uint16)
+        self._check(self.lib.hso_gpu_rectify_map_read(self.h, int(map_id), _ptr(xy), _ptr(frac)), "rectify_map_read")
+        return xy, frac
+
+    def frame_upload_rectified(self, frame_id, img, map_id, device_ptr=None, width=None, height=None):
+        """Raw sensor image -> (cv::resize to the map's size when it differs) -> cv::remap through the map -> Frame."""
+        st = FrameStats()
+        if device_ptr is not None:
+            rc = self.lib.hso_gpu_frame_upload_rectified(self.h, frame_id, C.c_void_p(device_ptr), width, height, int(map_id), 1, C.byref(st))
+        else:
+            img = np.ascontiguousarray(img, dtype=np.uint8)
+            h, w = img.shape
+            rc = self.lib.hso_gpu_frame_upload_rectified(self.h, frame_id, _ptr(img), w, h, int(map_id), 0, C.byref(st))
+        self._check(rc, "frame_upload_rectified")
+        return st
+
+    def frame_upload_batch_rectified(self, frame_ids, map_id, imgs=None, device_ptrs=None, want_stats=True):
+        n = len(frame_ids)
+        ids = np.ascontiguousarray(frame_ids, np.int64)
+        if device_ptrs is not None:
+            ptrs = np.ascontiguousarray(device_ptrs, np.uint64)
+            is_dev = 1
+        else:
+            imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in imgs]
+            ptrs = np.array([im.ctypes.data for im in imgs], np.uint64)
+            is_dev = 0
+        stats = (FrameStats * n)() if want_stats else None
+        rc = self.lib.hso_gpu_frame_upload_batch_rectified(self.h, _ptr(ids), _ptr(ptrs), n, int(map_id), is_dev,
+                                                           C.cast(stats, C.c_void_p) if want_stats else None)
+        self._check(rc, "frame_upload_batch_rectified")
         return list(stats) if want_stats else None
 
     def frame_release(self, frame_id):

@@ -49,6 +49,7 @@ struct FrameRec {
 struct TrackBatchState;  // hso_tracker.hip
 struct SeedTables;       // hso_seed.hip: resident seed tables
 struct SeqMaps;          // hso_align.hip: sequence maps (tables mirrored row for row, patched in place)
+struct RectifyMaps;      // hso_rectify.hip: rectification maps (hso_gpu_rectify_map_create*)
 
 struct hso_gpu_ctx {
   int device;
@@ -90,6 +91,7 @@ struct hso_gpu_ctx {
   char* h_pack; size_t h_pack_cap;
   // hso_octree_dev.hip: keys, labels, node lists and selections of the oct-tree kernel, grow-only
   char* d_octree = nullptr; size_t octree_cap = 0;
+  RectifyMaps* rectify = nullptr;
 };
 
 // Many short device lists (per frame and level: corners, edgelets ...) to caller memory in ONE DMA: a gather kernel packs them back
@@ -220,6 +222,7 @@ int hso_seed_table_rows(hso_gpu_ctx* ctx, int table, const int32_t* slots, int n
 int hso_seed_async_quiesce(hso_gpu_ctx* ctx);   // wait for a previous-frame pass in flight (its results stay collectable)
 bool hso_seed_tables_pin(hso_gpu_ctx* ctx, int64_t frame_id);   // a resident seed table hosts live seeds in this frame
 void hso_seqmaps_free(hso_gpu_ctx* ctx);
+void hso_rectify_free(hso_gpu_ctx* ctx);        // hso_rectify.hip: the context's rectification maps
 // a frame allocation of geometry g: recycled when the free list holds that geometry, else fresh with zeroed padding rows.
 // hso_frame_free returns it to the list (or the allocator); neither touches ctx->frames.
 // ---- the resident per-frame chain (hso_gpu_seq_chain: orchestrated in hso_select.hip; the sequence maps' storage and the kernels

@@ -365,6 +365,7 @@ void hso_gpu_destroy(hso_gpu_ctx* ctx)
   hso_seed_tables_free(ctx);
   hso_seqmaps_free(ctx);
   hso_chain_forget(ctx);
+  hso_rectify_free(ctx);
   for (auto* p : ctx->frame_slabs) (void)hipFree(p);
   if (ctx->d_batch) (void)hipFree(ctx->d_batch);
   hso_rba_forget(ctx);

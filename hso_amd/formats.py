@@ -20,7 +20,7 @@ import zlib
 
 import numpy as np
 
-from .capi import CAM_PINHOLE, CAM_FOV, make_camera
+from .capi import CAM_PINHOLE, CAM_FOV, CAM_EQUIDISTANT, make_camera
 
 G_MAX_RESOLUTION = 848 * 800          # test/test_dataset.cpp:55
 
@@ -33,7 +33,7 @@ def parse_calibration(path_or_text):
     """-> dict(camera=hso_camera, model, width, height, file_width, file_height, undistort).
     Line 1: "Pinhole fx fy cx cy d0 d1 d2 d3" | "Equidistant ..." (9 tokens) or
     "FOV fx fy cx cy omega" (6 tokens); line 2: "width height"; FOV line 3: "true" = undistort the
-    image first.  Values pass through float like the reference's sscanf("%f")."""
+    image first (an Equidistant camera always does).  Values pass through float like the reference's sscanf("%f")."""
     text = open(path_or_text).read() if os.path.exists(str(path_or_text)) else str(path_or_text)
     lines = text.splitlines()
     tok = lines[0].split()
@@ -55,8 +55,11 @@ def parse_calibration(path_or_text):
         if scale_intrinsics:
             ic[0:4] = [_f32(np.float64(v) / resize_rate) for v in ic[0:4]]
     if kind == "e":
-        raise NotImplementedError("EquidistantCamera is outside the hot path's camera models (pinhole / radtan / FOV)")
-    if kind == "p":
+        # EquidistantCamera (src/camera.cpp:274-292): pinhole projection, undistort_ always true — k0..k3 live in the rectification
+        # map alone (hso_gpu_rectify_build_map), which the harness applies to every image (test/test_dataset.cpp:276)
+        cam = make_camera(CAM_EQUIDISTANT, width_i, height_i, ic[0], ic[1], ic[2], ic[3], d=[float(v) for v in ic[4:8]] + [0.0], distortion=0)
+        undistort = True
+    elif kind == "p":
         cam = make_camera(CAM_PINHOLE, width_i, height_i, ic[0], ic[1], ic[2], ic[3], d=[float(v) for v in ic[4:8]] + [0.0])
         undistort = False
     else:
@@ -65,7 +68,7 @@ def parse_calibration(path_or_text):
             fx, fy, cx, cy = fx * width_i, fy * height_i, cx * width_i, cy * height_i
         undistort = len(lines) > 2 and lines[2].strip() == "true"
         cam = make_camera(CAM_FOV, width_i, height_i, fx, fy, cx, cy, d=[float(ic[4])], distortion=0 if undistort else 1)
-    return dict(camera=cam, model={"p": "Pinhole", "f": "FOV"}[kind], width=width_i, height=height_i,
+    return dict(camera=cam, model={"p": "Pinhole", "f": "FOV", "e": "Equidistant"}[kind], width=width_i, height=height_i,
                 file_width=int(wh[0]), file_height=int(wh[1]), undistort=undistort)
 
 

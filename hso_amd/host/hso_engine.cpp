@@ -95,7 +95,8 @@ Bank::Bank(hso_gpu_ctx* ctx, bool owns_ctx, const hso_camera& cam, const Setting
     for (Seq* s : seq_) { if (s->map >= 0) (void)hso_gpu_seqmap_destroy(ctx_, s->map); delete s; }
     for (StepData* d : step_) delete d;
     seq_.clear(); step_.clear();
-    if (seed_table_ >= 0) (void)hso_gpu_seed_table_destroy(ctx_, seed_table_);
+    if (rectify_map_ >= 0) (void)hso_gpu_rectify_map_destroy(ctx_, rectify_map_);
+  if (seed_table_ >= 0) (void)hso_gpu_seed_table_destroy(ctx_, seed_table_);
     seed_table_ = -1;
     if (owns_ctx_) hso_gpu_destroy(ctx_);
   };
@@ -225,9 +226,27 @@ void Bank::pin_threads()
   pinned_driver_ = me; driver_pinned_ = true;
 }
 
-void Bank::set_options(bool sync_previous, bool track_no_coop, bool no_numa_pin, bool device_select)
+bool Bank::rectify_available()
 {
+  return hso_gpu_rectify_map_create && hso_gpu_rectify_map_destroy && hso_gpu_frame_upload_batch_rectified && hso_gpu_frame_download_level;
+}
+
+void Bank::set_options(bool sync_previous, bool track_no_coop, bool no_numa_pin, bool device_select, bool rectify)
+{
+  // before anything changes: the harness's `if(cam_->getUndistort())` (test/test_dataset.cpp:276) holds for a FOV camera built with
+  // undistort = true and for an Equidistant camera, and for no other
+  const hso_camera pod = cam_.pod();
+  if (rectify && !((pod.model == HSO_CAM_FOV && pod.distortion == 0) || pod.model == HSO_CAM_EQUIDISTANT))
+    throw Refused("set_options: rectify is for the cameras the reference rectifies (FOV with undistort = true, Equidistant)");
   previous_collect();                                            // a pass in flight is applied under the old setting
+  if (rectify && rectify_map_ < 0) {
+    int32_t map = -1;
+    check(hso_gpu_rectify_map_create(ctx_, &pod, &map), "rectification map");
+    rectify_map_ = map;
+  } else if (!rectify && rectify_map_ >= 0) {
+    check(hso_gpu_rectify_map_destroy(ctx_, rectify_map_), "rectification map");
+    rectify_map_ = -1;
+  }
   sync_previous_ = sync_previous;
   no_numa_pin_ = no_numa_pin;
   device_select_ = device_select;

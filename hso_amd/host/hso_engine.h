@@ -181,7 +181,9 @@ public:
   int trajectory(int k, double* stamps, hso_se3* T_f_w, int cap) const;
   bool trace(int k, const char* path);
   bool trace_state(int k, bool on);
-  void set_options(bool sync_previous, bool track_no_coop, bool no_numa_pin = false, bool device_select = false);
+  // rectify: throws Refused for a camera the reference does not rectify; the caller checks rectify_available() first
+  void set_options(bool sync_previous, bool track_no_coop, bool no_numa_pin = false, bool device_select = false, bool rectify = false);
+  static bool rectify_available();   // the device library linked in has hso_gpu_frame_upload_batch_rectified
   void call_counts(int64_t* calls, int64_t* items, int cap) const;
   // algorithmic bytes (SURVEY.md section 8(d) units) of the steps so far: [frame build, tracker, matcher, pose optimiser, seeds]
   void alg_bytes(double* out, int cap) const { for (int i = 0; i < cap && i < 5; i++) out[i] = alg_bytes_[i]; }
@@ -292,6 +294,7 @@ private:
   Pinned<hso_keypoint> det_sel_;                // ... and, with device_select_, the selected keys instead
   Pinned<float> det_occ_;
   bool device_select_ = false;                  // hso_vo_options.device_select
+  int rectify_map_ = -1;                        // hso_vo_options.rectify: the camera's rectification map on the device, -1 = images arrive rectified
   int det_corner_cap_ = 8192;                   // corners per (frame, level) the lists hold; grows when a frame has more
 };
 

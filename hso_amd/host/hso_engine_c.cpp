@@ -65,7 +65,12 @@ static int set_opts(Bank* b, const hso_vo_options* o)
   if (!b || !o || o->size < 12 || o->size > (int32_t)sizeof(hso_vo_options)) return HSO_E_INVALID;
   const bool no_pin = o->size >= 16 && o->no_numa_pin != 0;
   const bool device_select = o->size >= 20 && o->device_select != 0;
-  return guarded(b, [&]() { b->set_options(o->sync_previous != 0, o->track_no_coop != 0, no_pin, device_select); });
+  const bool rectify = o->size >= 24 && o->rectify != 0;
+  if (rectify && !Bank::rectify_available()) {   // nothing was touched
+    if (!b->poisoned) b->err = "set_options: the device library has no rectification entries (hso_gpu_frame_upload_batch_rectified)";
+    return HSO_E_UNSUPPORTED;
+  }
+  return guarded(b, [&]() { b->set_options(o->sync_previous != 0, o->track_no_coop != 0, no_pin, device_select, rectify); });
 }
 int hso_vo_set_options(hso_vo* v, const hso_vo_options* o) { return v ? set_opts(v->bank, o) : HSO_E_INVALID; }
 int hso_vo_trace_state(hso_vo* v, int on) { return (v && v->bank->trace_state(0, on != 0)) ? HSO_OK : HSO_E_INVALID; }

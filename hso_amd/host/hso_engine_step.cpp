@@ -152,16 +152,29 @@ void Bank::upload(const std::vector<int>& who, const uint8_t* const* imgs, int w
     ids.push_back(F.dev_id); ptr.push_back(imgs[k]);
   }
   std::vector<hso_frame_stats> st(who.size());
-  check(hso_gpu_frame_upload_batch(ctx_, ids.data(), ptr.data(), (int)who.size(), w, h, on_device ? 1 : 0, st.data()), "Frame");
+  // hso_vo_options.rectify: the images are raw, `cam_->undistortImage(image, image)` (test/test_dataset.cpp:276) runs in the same call
+  if (rectify_map_ >= 0)
+    check(hso_gpu_frame_upload_batch_rectified(ctx_, ids.data(), ptr.data(), (int)who.size(), rectify_map_, on_device ? 1 : 0, st.data()), "Frame (rectified)");
+  else
+    check(hso_gpu_frame_upload_batch(ctx_, ids.data(), ptr.data(), (int)who.size(), w, h, on_device ? 1 : 0, st.data()), "Frame");
   n_calls_[0]++; n_items_[0] += (int64_t)who.size();
+  std::vector<uint8_t> rectified;
   for (size_t i = 0; i < who.size(); i++) {
     Seq& s = *seq_[who[i]];
     Frame& F = s.frames[s.cur];
     F.integral = st[i].integral_image; F.grad_mean = st[i].grad_mean;
     if (s.trace.on()) {
+      // the record holds what the Frame was built from — with rectify, level 0 as the device made it — so that a replay through
+      // hso_gpu_frame_upload reproduces the frame
+      const uint8_t* img = imgs[who[i]];
+      if (rectify_map_ >= 0) {
+        rectified.resize((size_t)w * h);
+        check(hso_gpu_frame_download_level(ctx_, F.dev_id, 0, rectified.data(), nullptr, nullptr), "trace");
+        img = rectified.data();
+      }
       s.trace.begin("frame_upload", 5);
       s.trace.scalar("frame_id", (double)F.dev_id); s.trace.scalar("width", w); s.trace.scalar("height", h);
-      s.trace.field("img", imgs[who[i]], (size_t)w * h); s.trace.field("stats", &st[i], sizeof(st[i]));
+      s.trace.field("img", img, (size_t)w * h); s.trace.field("stats", &st[i], sizeof(st[i]));
     }
   }
 }

@@ -2,8 +2,10 @@
 
 The reference's test_dataset harness (test/test_dataset.cpp:260-335: BenchmarkNode::runFromFolder +
 saveResult) without OpenCV: read the calibration (incl. the > 848x800 downscale rule), list the images of the
-folder, resize every image to the camera size on the device when the sensor is larger, feed
-FrameHandlerMono::addImage in order, write the keyframe trajectory in the reference's format.
+folder, resize every image to the camera size on the device when the sensor is larger, rectify it on the device when the
+camera asks for it (`if(cam_->getUndistort()) cam_->undistortImage(image, image)`, test_dataset.cpp:276: a FOV file whose third
+line is `true`, any Equidistant file), feed FrameHandlerMono::addImage in order, write the keyframe trajectory in the reference's
+format.
 
 Options (the reference's `key=value` style, test_dataset.cpp:66-114):
   start=<i> end=<i>        frame range (test/euroc_batch.sh:9 uses start=50 for MH_01)
@@ -47,6 +49,10 @@ def main(argv, return_line=False):
     if "depth0" in opt:
         d0 = np.load(opt["depth0"]) if opt["depth0"].endswith(".npy") else np.fromfile(opt["depth0"], np.float32).reshape(H, W)
     odo = vo.VisualOdometry(cam, int(opt.get("max_fts", 200)))
+    if calib["undistort"]:
+        # cam_->undistortImage between readImage and addImage (test/test_dataset.cpp:276): the engine takes raw camera-size images
+        # and rectifies them in its upload (hso_vo_options.rectify); depth0, when given, is in rectified geometry
+        odo.set_options(rectify=True)
     if "trace" in opt:
         odo.trace(opt["trace"])
     resize_ctx = None

@@ -17,8 +17,9 @@ EUROC = dict(model=CAM_PINHOLE, width=752, height=480, fx=458.654, fy=457.296, c
 
 
 # test/cameras/tum_mono_vo_wide.txt at the reference's internal 920x736 (test/test_dataset.cpp:218-224).  Its third line is
-# "true": the image is rectified first (cv::remap, outside the hot path) and the FOV camera then projects without distortion
-# (src/camera.cpp:171-221, undistort_ branch).
+# "true": every image is rectified first (cv::remap per frame, test/test_dataset.cpp:276 — on the device here:
+# hso_gpu_frame_upload_rectified, hso_vo_options.rectify) and the FOV camera then projects without distortion
+# (src/camera.cpp:171-221, undistort_ branch).  The images synthesised for this camera are already rectified.
 TUM_WIDE = dict(model=CAM_FOV, width=920, height=736, fx=0.349153 * 920, fy=0.436593 * 736, cx=0.49314 * 920, cy=0.499021 * 736,
                 d=(0.933271,), distortion=0)
 # the same sensor geometry with the FOV distortion left in the projection (third line "false").  omega is reduced so that

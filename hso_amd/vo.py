@@ -25,9 +25,19 @@ class VoStatus(C.Structure):
 
 
 class VoOptions(C.Structure):
-    # hso_vo_options (include/hso_vo.h)
+    # hso_vo_options (include/hso_vo.h).  The header names the word after device_select `rectify` and keeps two reserved words behind
+    # it; the binding keeps the three words as one array — its layout is pinned by tests/test_device_select_cpu.py — and names the
+    # first through a property.
     _fields_ = [("size", C.c_int32), ("sync_previous", C.c_int32), ("track_no_coop", C.c_int32), ("no_numa_pin", C.c_int32), ("device_select", C.c_int32),
                 ("reserved", C.c_int32 * 3)]
+
+    @property
+    def rectify(self):
+        return self.reserved[0]
+
+    @rectify.setter
+    def rectify(self, v):
+        self.reserved[0] = int(v)
 
 
 _lib = None
@@ -140,8 +150,10 @@ class MultiVisualOdometry:
     def trace(self, k, path):
         self._check(self.lib.hso_vo_multi_trace(self.h, int(k), path.encode() if path else None), "trace")
 
-    def set_options(self, sync_previous=False, track_no_coop=False, no_numa_pin=False, device_select=False):
+    def set_options(self, sync_previous=False, track_no_coop=False, no_numa_pin=False, device_select=False, rectify=False):
+        """rectify: the images handed over from now on are raw and the engine rectifies them on the device (hso_vo_options.rectify)"""
         o = VoOptions(C.sizeof(VoOptions), int(bool(sync_previous)), int(bool(track_no_coop)), int(bool(no_numa_pin)), int(bool(device_select)))
+        o.rectify = int(bool(rectify))
         self._check(self.lib.hso_vo_multi_set_options(self.h, C.byref(o)), "set_options")
 
     def start(self, which=None):
@@ -228,8 +240,10 @@ class VisualOdometry:
         self._check(self.lib.hso_vo_trace_state(self.h, 1 if state else 0), "trace_state")
         self._check(self.lib.hso_vo_trace(self.h, path.encode() if path else None), "trace")
 
-    def set_options(self, sync_previous=False, track_no_coop=False, no_numa_pin=False, device_select=False):
+    def set_options(self, sync_previous=False, track_no_coop=False, no_numa_pin=False, device_select=False, rectify=False):
+        """rectify: the images handed over from now on are raw and the engine rectifies them on the device (hso_vo_options.rectify)"""
         o = VoOptions(C.sizeof(VoOptions), int(bool(sync_previous)), int(bool(track_no_coop)), int(bool(no_numa_pin)), int(bool(device_select)))
+        o.rectify = int(bool(rectify))
         self._check(self.lib.hso_vo_set_options(self.h, C.byref(o)), "set_options")
 
     def set_first_frame(self, img, depth_z, timestamp=0.0, T_f_w=None):

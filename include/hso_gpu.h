@@ -51,9 +51,10 @@ enum { HSO_CAM_PINHOLE = 0, HSO_CAM_FOV = 1, HSO_CAM_EQUIDISTANT = 2 };
 typedef struct hso_camera {
   int32_t model;       /* HSO_CAM_* */
   int32_t width, height;
-  int32_t distortion;  /* pinhole: |d0| > 1e-7 (camera.cpp:37); FOV: !undistort_ (camera.cpp:208) */
+  int32_t distortion;  /* pinhole: |d0| > 1e-7 (camera.cpp:37); FOV: !undistort_ (camera.cpp:208); Equidistant: 0 (camera.cpp:312-315) */
   double fx, fy, cx, cy;
-  double d[5];         /* pinhole radtan k1,k2,p1,p2,k3 (camera.cpp:105-120); FOV: d[0] = omega */
+  double d[5];         /* pinhole radtan k1,k2,p1,p2,k3 (camera.cpp:105-120); FOV: d[0] = omega; Equidistant: k0..k3 (camera.cpp:282),
+                          read by the rectification map alone (hso_gpu_rectify_build_map) */
 } hso_camera;
 
 typedef struct hso_se3 {
@@ -152,6 +153,48 @@ int hso_gpu_frame_upload_resized(hso_gpu_ctx* ctx, int64_t frame_id, const uint8
 int hso_gpu_frame_upload_batch(hso_gpu_ctx* ctx, const int64_t* frame_ids,
                                const uint8_t* const* imgs, int n, int width, int height,
                                int img_is_device, hso_frame_stats* stats_out /* n or NULL */);
+
+/* ---- rectification: `if(cam_->getUndistort()) cam_->undistortImage(image, image);` between ImageReader::readImage and
+ *      FrameHandlerMono::addImage (test/test_dataset.cpp:275-276).  Two camera classes take that branch: FOVCamera built with
+ *      undistort = true (model HSO_CAM_FOV, distortion 0, d[0] = omega) and EquidistantCamera (model HSO_CAM_EQUIDISTANT,
+ *      distortion 0, d[0..3] = k0..k3), whose undistort_ is always true (src/camera.cpp:289) and whose projection is plain
+ *      pinhole (:297-315).  For every other camera the reference never rectifies, and neither do these entries. ---- */
+/* The fixed-point maps of a camera: FOVCamera::getRemap + distortPixelFOV (src/camera.cpp:223-265) or EquidistantCamera::getRemap +
+ * distortPixelEquidistant (:317-364), then cv::convertMaps(..., CV_16SC2) (:244, :339), restated operation by operation and type
+ * by type (tanf / atanf are the host libm's, as in the reference).  xy: 2 * width * height (source column, source row of the
+ * top-left tap per pixel, saturated to short), frac: width * height ((iy & 31) * 32 + (ix & 31), the 1/32-pixel fractions).
+ * Host code, no context needed.  HSO_E_INVALID for NULL pointers and for a camera the reference does not rectify (pinhole; FOV
+ * with distortion = 1). */
+int hso_gpu_rectify_build_map(const hso_camera* cam, int16_t* xy, uint16_t* frac);
+/* cv::remap(src, dst, map1 CV_16SC2, map2 CV_16UC1, INTER_LINEAR) for CV_8UC1, BORDER_CONSTANT with value 0, of
+ * FOVCamera / EquidistantCamera::undistortImage (src/camera.cpp:267-271, :366-370): integer arithmetic, taps outside the image read
+ * 0.  Host code, no context needed: the definition the device kernel is held to byte for byte.  src and dst (width * height bytes
+ * each) must not alias (cv::remap clones an in-place source). */
+int hso_gpu_rectify_host(const int16_t* xy, const uint16_t* frac, int width, int height, const uint8_t* src, uint8_t* dst);
+/* A camera's maps on the device (what the camera's constructor keeps in undist_map1_ / undist_map2_, src/camera.cpp:165, :291):
+ * hso_gpu_rectify_build_map, uploaded; *map_out names them in the calls below.  HSO_E_INVALID for the cameras build_map refuses
+ * and for sizes the frame uploads refuse (width % 4 != 0, smaller than 64x64). */
+int hso_gpu_rectify_map_create(hso_gpu_ctx* ctx, const hso_camera* cam, int32_t* map_out);
+/* The same from a caller's own fixed-point maps in cv::convertMaps' CV_16SC2 + CV_16UC1 layout (any source coordinates: taps
+ * outside the image read 0; only the low 10 bits of a frac entry are used, as in cv::remap). */
+int hso_gpu_rectify_map_create_tables(hso_gpu_ctx* ctx, int width, int height, const int16_t* xy, const uint16_t* frac, int32_t* map_out);
+/* Waits for the context's stream.  Maps are also freed with the context.  HSO_E_INVALID: unknown or already destroyed. */
+int hso_gpu_rectify_map_destroy(hso_gpu_ctx* ctx, int32_t map);
+/* The harness's readImage -> undistortImage -> new Frame (test/test_dataset.cpp:275-276, src/ImageReader.cpp:79,
+ * src/camera.cpp:267-271 / :366-370, src/frame.cpp:82-96) in one call: a raw image of another size than the map's first goes
+ * through the cv::resize of hso_gpu_frame_upload_resized, then the remap (hso_gpu_rectify_host's bytes) writes level 0 of the new
+ * frame, then the frame is built as hso_gpu_frame_upload builds it.  Errors as hso_gpu_frame_upload_resized, and HSO_E_INVALID
+ * for an unknown or destroyed map. */
+int hso_gpu_frame_upload_rectified(hso_gpu_ctx* ctx, int64_t frame_id, const uint8_t* img, int src_width, int src_height, int32_t map,
+                                   int img_is_device, hso_frame_stats* stats_out);
+/* hso_gpu_frame_upload_batch for raw images (the same undistortImage, src/camera.cpp:267-271 / :366-370, per frame): n images of
+ * the map's size, one remap launch for all of them straight into the frames' level-0 planes, then the batched build.  Same
+ * contract: a resident id is refreshed in place, nothing new is resident after an error, asynchronous with device images and
+ * stats_out == NULL.  Host images are staged raw in the context's work area.  HSO_E_INVALID for an unknown or destroyed map, and
+ * when a resident frame has another size than the map. */
+int hso_gpu_frame_upload_batch_rectified(hso_gpu_ctx* ctx, const int64_t* frame_ids, const uint8_t* const* imgs, int n, int32_t map,
+                                         int img_is_device, hso_frame_stats* stats_out /* n or NULL */);
+
 int hso_gpu_frame_release(hso_gpu_ctx* ctx, int64_t frame_id);
 /* n frames with one wait for the stream (~Frame of the frames n sequences dropped in a step); all or nothing: HSO_E_NOFRAME /
  * HSO_E_INVALID (a frame hosts live seeds of a resident table) leave every frame resident. */

@@ -78,6 +78,10 @@ int hso_gpu_debug_sobel_taps(hso_gpu_ctx* ctx, int64_t frame, int level, int16_t
 /* test hook: the statistics record a resident frame carries on the device now (what its upload returned, unless something wrote it since) */
 int hso_gpu_debug_frame_stats(hso_gpu_ctx* ctx, int64_t frame, hso_frame_stats* out);
 
+/* test hook: a rectification map as the device holds it (hso_gpu_rectify_map_create / _create_tables): xy 2 * width * height,
+ * frac width * height entries of the map's own size.  Synchronises the context's stream. */
+int hso_gpu_rectify_map_read(hso_gpu_ctx* ctx, int32_t map, int16_t* xy, uint16_t* frac);
+
 /* test hook: the wave64 lane-exchange primitives of the device code (hso_amd/csrc/hso_wave.h), each by itself.  One workgroup of
  * HSO_WAVE_DBG_THREADS threads (two wavefronts); thread t reads in[t * HSO_WAVE_DBG_VALUES + i] (small integers, so that every sum
  * is exact in fp32 and fp64) and writes out[t * HSO_WAVE_DBG_FIELDS + field].  With lane = t % 64, wave = t / 64, v[i] thread t's

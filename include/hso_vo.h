@@ -49,11 +49,19 @@ typedef struct hso_vo_options {
                                  oct-tree in one call, only the selected keys come back) instead of on the worker pool; same results: tests compare.
                                  The initialisation, a step in which a sequence records a trace, and a device library without the entry
                                  keep the host path */
-  int32_t reserved[3];
+  int32_t rectify;            /* 1: the images handed to hso_vo_set_first_frame, hso_vo_add_image and the hso_vo_multi_* forms (device pointers
+                                 included) are RAW camera-size images, and the engine runs the harness's `if(cam_->getUndistort())
+                                 cam_->undistortImage(image, image);` (test/test_dataset.cpp:276) on the device: it creates the camera's map
+                                 (hso_gpu_rectify_map_create) when the option is set and uploads through hso_gpu_frame_upload_batch_rectified.
+                                 A recorded sequence's frame_upload records hold the rectified image.  hso_vo_set_options returns
+                                 HSO_E_INVALID for a camera the reference does not rectify (pinhole; FOV with undistort = false) and
+                                 HSO_E_UNSUPPORTED when the device library lacks the entries; set it before the first frame */
+  int32_t reserved[2];
 } hso_vo_options;
 int hso_vo_set_options(hso_vo* vo, const hso_vo_options* options);
 /* first keyframe: features are detected the way the initialisation detects them and every feature with
- * depth_z[y * width + x] > 0 (depth along the optical axis, metres) becomes a map point hosted in this frame */
+ * depth_z[y * width + x] > 0 (depth along the optical axis, metres) becomes a map point hosted in this frame.
+ * depth_z is indexed by the pixels of the Frame: with hso_vo_options.rectify it is in RECTIFIED geometry (the image is raw). */
 int hso_vo_set_first_frame(hso_vo* vo, const uint8_t* img, int width, int height, double timestamp, const float* depth_z,
                            const hso_se3* T_f_w /* NULL = identity */);
 /* FrameHandlerBase::start(): the next image is the first frame of the two-view initialisation (stage 1, then 2 until the
