@@ -326,6 +326,7 @@ def load():
     lib.hso_gpu_rectify_map_read.argtypes = [vp, C.c_int32, vp, vp]
     lib.hso_gpu_frame_upload_rectified.argtypes = [vp, i64, vp, i32, i32, C.c_int32, i32, P(FrameStats)]
     lib.hso_gpu_frame_upload_batch_rectified.argtypes = [vp, vp, vp, i32, C.c_int32, i32, vp]
+    lib.hso_gpu_frame_upload_batch_resized.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, C.c_int32, i32, vp]
     lib.hso_gpu_frame_release.argtypes = [vp, i64]
     lib.hso_gpu_frame_release_batch.argtypes = [vp, vp, i32]
     lib.hso_gpu_frame_download_level.argtypes = [vp, i64, i32, vp, P(i32), P(i32)]
@@ -422,6 +423,7 @@ EXPORTED_SYMBOLS = [
     "hso_gpu_select_octree_batch", "hso_gpu_detect_select_multi",
     "hso_gpu_rectify_build_map", "hso_gpu_rectify_host", "hso_gpu_rectify_map_create", "hso_gpu_rectify_map_create_tables",
     "hso_gpu_rectify_map_destroy", "hso_gpu_frame_upload_rectified", "hso_gpu_frame_upload_batch_rectified",
+    "hso_gpu_frame_upload_batch_resized",
 ]
 
 
@@ -648,6 +650,27 @@ class Context:
         rc = self.lib.hso_gpu_frame_upload_batch_rectified(self.h, _ptr(ids), _ptr(ptrs), n, int(map_id), is_dev,
                                                            C.cast(stats, C.c_void_p) if want_stats else None)
         self._check(rc, "frame_upload_batch_rectified")
+        return list(stats) if want_stats else None
+
+    def frame_upload_batch_resized(self, frame_ids, width, height, imgs=None, device_ptrs=None, src_width=None, src_height=None, map_id=-1,
+                                   want_stats=True):
+        """n sensor-size images of one size -> cv::resize to width x height (ImageReader::readImage, src/ImageReader.cpp:79) ->
+        (map_id >= 0: cv::remap through the map) -> Frames, one call."""
+        n = len(frame_ids)
+        ids = np.ascontiguousarray(frame_ids, np.int64)
+        if device_ptrs is not None:
+            ptrs = np.ascontiguousarray(device_ptrs, np.uint64)
+            is_dev = 1
+        else:
+            imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in imgs]
+            ptrs = np.array([im.ctypes.data for im in imgs], np.uint64)
+            src_height, src_width = imgs[0].shape
+            assert all(im.shape == imgs[0].shape for im in imgs)
+            is_dev = 0
+        stats = (FrameStats * n)() if want_stats else None
+        rc = self.lib.hso_gpu_frame_upload_batch_resized(self.h, _ptr(ids), _ptr(ptrs), n, int(src_width), int(src_height), int(width), int(height),
+                                                         int(map_id), is_dev, C.cast(stats, C.c_void_p) if want_stats else None)
+        self._check(rc, "frame_upload_batch_resized")
         return list(stats) if want_stats else None
 
     def frame_release(self, frame_id):

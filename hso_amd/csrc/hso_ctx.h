@@ -216,6 +216,9 @@ int hso_frame_store_gradients(hso_gpu_ctx* ctx, const PyrGeom& g, uint8_t* const
 int hso_frame_require_gradients(hso_gpu_ctx* ctx, const int64_t* frame_ids, int n);
 // cv::resize INTER_LINEAR of a device image into a device buffer (hso_frame.hip)
 int hso_frame_resize_into(hso_gpu_ctx* ctx, const uint8_t* d_src, int sw, int sh, uint8_t* d_dst, int dw, int dh);
+// the same for n device images of one size in one launch: image i -> d_dsts[i] + dst_off (dw % 4 == 0, destinations 4-byte aligned)
+int hso_frame_resize_batch(hso_gpu_ctx* ctx, const uint8_t* const* d_srcs, int sw, int sh, uint8_t* const* d_dsts, uint32_t dst_off,
+                           int dw, int dh, int n);
 void hso_track_state_free(hso_gpu_ctx* ctx);
 void hso_seed_tables_free(hso_gpu_ctx* ctx);
 int hso_seed_table_rows(hso_gpu_ctx* ctx, int table, const int32_t* slots, int n, const char** rows, size_t* stride, size_t* seed_offset, PyrGeom* g);

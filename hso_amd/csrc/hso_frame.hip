@@ -172,9 +172,145 @@ int hso_frame_resize_into(hso_gpu_ctx* ctx, const uint8_t* d_src, int sw, int sh
   return HSO_OK;
 }
 
+// ---- the same cv::resize for a batch (hso_gpu_frame_upload_batch_resized): n source images of one size in one launch, grid.y the
+// frame, written where the next stage reads (level 0 of the frame, or the rectification's source slot).  resize_linear_px above
+// stays the definition; this kernel is held to it byte for byte (tests/test_resize_batch_gpu.py).
+//
+// Shape.  A wavefront owns RSZ_ROWS output rows of 64 column quads: a lane produces four adjacent pixels of a row and stores them as
+// one dword (256 contiguous bytes per wavefront and row; every destination width of this library is a multiple of 4 and every
+// destination 4-byte aligned).  What resize_linear_px derives per pixel is derived once here: the scales and the branch once per
+// lane, the lane's four (sx, a0, a1) once per lane — they do not depend on the row — and the strip's (sy0, b0, b1) once per
+// wavefront: lane r works out row r's triple in the prologue and the row loop fetches it with v_readlane, so the row's source
+// addresses are scalar and the loop holds integer arithmetic only.  resize_coef is the definition's float / double statements in
+// the definition's order and types (the library is compiled without contraction or fast math).
+// Loads.  The source is read with plain byte loads (global_load_ubyte): an image row of odd width starts at any byte, the two taps
+// of a pixel sit at a data-dependent column, and the bytes a wavefront touches in a row are one contiguous run of about
+// 256 * scale_x bytes, so the lines are fetched once and the rest comes out of L1 — the form k_rectify uses and was measured with.
+// Two things cut the load count instead: the horizontal pass of a source row is kept when the next output row starts on it (as
+// cv::resize's row cache does: at 1280x1024 -> 920x736 1.39 source rows per output row instead of 2), and a tap past the right
+// edge re-reads column sw - 1 with weight 0, which is the definition's `tail` (tail <=> sx >= sw - 1 <=> a0 = 2048, a1 = 0), so no
+// lane branches on its column class.  The exact 2 x 2 decimation reads eight bytes per row and lane; a source that is 8-byte
+// aligned (sw = 2 dw is a multiple of 8, so all rows are when the image is: every staged image, every allocation) takes them as one
+// aligned 8-byte load, any other source byte by byte.  An LDS row tile was not built.
+// Occupancy.  No LDS, 256 threads, registers well below 64: the block count, not the register file, limits a launch — one frame of
+// 920x736 is 4 x 12 blocks, so a batch of a few frames fills the device and a single frame does not (the single-frame entries keep
+// k_resize_image).
+#define RSZ_ROWS 16    // output rows per wavefront (<= 64: one lane per row in the prologue)
+#define RSZ_WAVES 4    // wavefronts (row strips) per block
+
+typedef const __attribute__((address_space(1))) uint8_t* RszGlbCU8;
+typedef const __attribute__((address_space(1))) unsigned long long* RszGlbCU64;
+typedef __attribute__((address_space(1))) uint32_t* RszGlbU32;
+
+// (source index, weight of it, weight of its successor) of output index d: resize_linear_px's statements.  limit > 0: the column
+// form with its two clamps; limit == 0: the row form (rows are clamped where they are read)
+HSO_DEV void resize_coef(int d, double scale, int limit, int& s, int& c0, int& c1)
+{
+  float f = (float)((d + 0.5) * scale - 0.5);
+  s = (int)floor((double)f);
+  f -= (float)s;
+  if (limit > 0) {
+    if (s < 0) { f = 0; s = 0; }
+    if (s >= limit - 1) { f = 0; s = limit - 1; }
+  }
+  c0 = max(-32768, min(32767, __float2int_rn((1.f - f) * 2048)));
+  c1 = max(-32768, min(32767, __float2int_rn(f * 2048)));
+}
+
+__global__ __launch_bounds__(256) void k_resize_batch(const uint8_t* const* __restrict__ srcs, int sw, int sh,
+                                                      uint8_t* const* __restrict__ dsts, uint32_t dst_off, int dw, int dh)
+{
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int quads = dw >> 2, xb = (quads + 63) >> 6;
+  const int q = (blockIdx.x % xb) * 64 + lane;
+  const int y0 = ((blockIdx.x / xb) * RSZ_WAVES + wv) * RSZ_ROWS;
+  if (y0 >= dh) return;                       // the whole wavefront
+  // a lane right of the image works on the last quad and stores nothing: every lane stays active for v_readlane, no load is
+  // out of bounds
+  const bool live = q < quads;
+  const int qc = live ? q : quads - 1;
+  // pointers read from a table are generic; say "global" so that the accesses are global_load / global_store
+  const RszGlbCU8 S = (RszGlbCU8)srcs[blockIdx.y];
+  const RszGlbU32 D = (RszGlbU32)(dsts[blockIdx.y] + dst_off) + qc;
+  const double scale_x = 1. / ((double)dw / sw), scale_y = 1. / ((double)dh / sh);
+  const int iscale_x = __double2int_rn(scale_x), iscale_y = __double2int_rn(scale_y);
+  const bool area_fast = fabs(scale_x - iscale_x) < 2.220446049250313e-16 && fabs(scale_y - iscale_y) < 2.220446049250313e-16;
+  if (area_fast && iscale_x == 2 && iscale_y == 2) {
+    const bool aligned = ((uintptr_t)srcs[blockIdx.y] & 7) == 0;
+    for (int r = 0; r < RSZ_ROWS; r++) {
+      const int dy = y0 + r;
+      if (dy >= dh) break;
+      const RszGlbCU8 s0 = S + (size_t)(2 * dy) * sw + 8 * qc, s1 = s0 + sw;
+      uint32_t t[2][2];
+      if (aligned) {
+        const unsigned long long u = *(RszGlbCU64)s0, v = *(RszGlbCU64)s1;
+        t[0][0] = (uint32_t)u; t[0][1] = (uint32_t)(u >> 32); t[1][0] = (uint32_t)v; t[1][1] = (uint32_t)(v >> 32);
+      } else {
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+          t[0][h] = (uint32_t)s0[4 * h] | ((uint32_t)s0[4 * h + 1] << 8) | ((uint32_t)s0[4 * h + 2] << 16) | ((uint32_t)s0[4 * h + 3] << 24);
+          t[1][h] = (uint32_t)s1[4 * h] | ((uint32_t)s1[4 * h + 1] << 8) | ((uint32_t)s1[4 * h + 2] << 16) | ((uint32_t)s1[4 * h + 3] << 24);
+        }
+      }
+      uint32_t word = 0;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const uint32_t a = t[0][k >> 1] >> (16 * (k & 1)), b = t[1][k >> 1] >> (16 * (k & 1));
+        word |= (((a & 0xffu) + ((a >> 8) & 0xffu) + (b & 0xffu) + ((b >> 8) & 0xffu) + 2u) >> 2) << (8 * k);
+      }
+      if (live) D[(size_t)dy * quads] = word;
+    }
+    return;
+  }
+  int o0[4], o1[4], a0[4], a1[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    resize_coef(4 * qc + k, scale_x, sw, o0[k], a0[k], a1[k]);
+    o1[k] = min(o0[k] + 1, sw - 1);           // the tail re-reads column sw - 1 with a1 = 0: S[sx] * 2048
+  }
+  int sy_l, b0_l, b1_l;                       // lane r: the row y0 + r
+  resize_coef(y0 + (lane & (RSZ_ROWS - 1)), scale_y, 0, sy_l, b0_l, b1_l);
+  auto hpass = [&](int y, int (&h)[4]) {
+    const RszGlbCU8 row = S + (size_t)y * sw;
+#pragma unroll
+    for (int k = 0; k < 4; k++) h[k] = ((int)row[o0[k]] * a0[k] + (int)row[o1[k]] * a1[k]) >> 4;
+  };
+  int kept = -1, h0[4], h1[4] = {0, 0, 0, 0};  // kept: the source row h1 holds
+  for (int r = 0; r < RSZ_ROWS; r++) {
+    const int dy = y0 + r;
+    if (dy >= dh) break;
+    const int sy0 = __builtin_amdgcn_readlane(sy_l, r), b0 = __builtin_amdgcn_readlane(b0_l, r), b1 = __builtin_amdgcn_readlane(b1_l, r);
+    const int ya = min(max(sy0, 0), sh - 1), yb = min(max(sy0 + 1, 0), sh - 1);
+    if (ya == kept) {
+#pragma unroll
+      for (int k = 0; k < 4; k++) h0[k] = h1[k];
+    } else hpass(ya, h0);
+    if (yb == ya) {
+#pragma unroll
+      for (int k = 0; k < 4; k++) h1[k] = h0[k];
+    } else hpass(yb, h1);
+    kept = yb;
+    uint32_t word = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) word |= (uint32_t)((((b0 * h0[k]) >> 16) + ((b1 * h1[k]) >> 16) + 2) >> 2) << (8 * k);
+    if (live) D[(size_t)dy * quads] = word;
+  }
+}
+
+int hso_frame_resize_batch(hso_gpu_ctx* ctx, const uint8_t* const* d_srcs, int sw, int sh, uint8_t* const* d_dsts, uint32_t dst_off,
+                           int dw, int dh, int n)
+{
+  const int xb = ((dw >> 2) + 63) >> 6, strips = (dh + RSZ_ROWS - 1) / RSZ_ROWS, yb = (strips + RSZ_WAVES - 1) / RSZ_WAVES;
+  for (int c0 = 0; c0 < n; c0 += 32768)     // blockIdx.y is a 16-bit quantity
+    hipLaunchKernelGGL(k_resize_batch, dim3(xb * yb, std::min(32768, n - c0)), dim3(256), 0, ctx->stream, d_srcs + c0, sw, sh, d_dsts + c0,
+                       dst_off, dw, dh);
+  HSO_HIP_CHECK(ctx, hipGetLastError());
+  return HSO_OK;
+}
+
 // -------------------------------------------------------------------- Sobel
 
-#define SOB_STRIP 15           // rows per lane
+#define SOB_STRIP 15          // rows per lane
 #define SOB_TW 64              // wavefront tile: 16 lanes x 4 pixels wide,
 #define SOB_TH (4 * SOB_STRIP) //                 4 lane groups x SOB_STRIP rows high (60: divides 480, 240, 120)
 #define SOB_WAVES 4            // tiles (wavefronts) per block

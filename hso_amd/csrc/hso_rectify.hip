@@ -285,4 +285,105 @@ int hso_gpu_frame_upload_batch_rectified(hso_gpu_ctx* ctx, const int64_t* frame_
   return HSO_OK;
 }
 
+// ImageReader::readImage's cv::resize(image, image, m_img_new_size) (reference src/ImageReader.cpp:79) for a batch, in front of the
+// optional undistortImage (test/test_dataset.cpp:275-276) and `new Frame`: one k_resize_batch launch, one k_rectify launch when a
+// map is named, the batched build, one wait when the statistics are wanted.
+int hso_gpu_frame_upload_batch_resized(hso_gpu_ctx* ctx, const int64_t* frame_ids, const uint8_t* const* imgs, int n, int src_width,
+                                       int src_height, int width, int height, int32_t map, int img_is_device, hso_frame_stats* stats_out)
+{
+  if (!ctx) return HSO_E_INVALID;
+  if (!frame_ids || !imgs || n <= 0) return hso_fail(ctx, HSO_E_INVALID, "frame_upload_batch_resized: null argument or n <= 0");
+  if (src_width <= 0 || src_height <= 0) return hso_fail(ctx, HSO_E_INVALID, "frame_upload_batch_resized: bad source size");
+  if ((width % 4) != 0 || width < 64 || height < 64)
+    return hso_fail(ctx, HSO_E_INVALID, "frame_upload_batch_resized: width must be a multiple of 4, width and height >= 64");
+  const RectifyMap* m = nullptr;
+  if (map >= 0) {
+    m = find_map(ctx, map);
+    if (!m) return hso_fail(ctx, HSO_E_INVALID, "frame_upload_batch_resized: no such map");
+    if (m->w != width || m->h != height) return hso_fail(ctx, HSO_E_INVALID, "frame_upload_batch_resized: the map has another size than the destination");
+  }
+  if (src_width == width && src_height == height)   // nothing to resize: the two entries this one stands in front of
+    return m ? hso_gpu_frame_upload_batch_rectified(ctx, frame_ids, imgs, n, map, img_is_device, stats_out)
+             : hso_gpu_frame_upload_batch(ctx, frame_ids, imgs, n, width, height, img_is_device, stats_out);
+  HSO_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const PyrGeom g = make_geom(width, height);
+  // as hso_gpu_frame_upload_batch: validate every entry, then allocate the new ones; ctx->frames is only touched once nothing
+  // can fail any more, so an error in the middle of a batch leaves no half-built frame resident
+  std::vector<uint8_t*> bases(n);
+  std::vector<int> fresh;
+  for (int i = 0; i < n; i++) {
+    if (!imgs[i]) return hso_fail(ctx, HSO_E_INVALID, "frame_upload_batch_resized: null image");
+    auto it = ctx->frames.find(frame_ids[i]);
+    if (it != ctx->frames.end() && !same_geom(it->second.g, g))
+      return hso_fail(ctx, HSO_E_INVALID, "frame_upload_batch_resized: resident frame has another size");
+    for (int k = 0; k < i && it == ctx->frames.end(); k++)
+      if (frame_ids[k] == frame_ids[i]) return hso_fail(ctx, HSO_E_INVALID, "frame_upload_batch_resized: a new frame id appears twice");
+  }
+  // work area: [bases | srcs | mids | stats | the source images, when they come from the host | the camera-size images, when they
+  // are rectified].  Reserved before anything is allocated or marked: a work area that cannot be had is HSO_E_NOMEM and nothing changed.
+  const size_t b_ptr = hso_al256((size_t)n * sizeof(void*)), b_stats = hso_al256((size_t)n * sizeof(hso_frame_stats));
+  const size_t src_bytes = (size_t)src_width * src_height, src_stride = hso_al256(src_bytes);
+  const size_t mid_stride = hso_al256((size_t)width * height);
+  const size_t b_raw = img_is_device ? 0 : (size_t)n * src_stride;
+  const size_t need = 3 * b_ptr + b_stats + b_raw + (m ? (size_t)n * mid_stride : 0);
+  if (hso_batch_reserve(ctx, need)) {
+    (void)hipGetLastError();
+    return hso_fail(ctx, HSO_E_NOMEM, "frame_upload_batch_resized: no device memory for the work area (n source images, and n camera-size images when rectifying)");
+  }
+  auto undo = [&]() { hso_stream_abandon(ctx->stream); for (int i : fresh) hso_frame_free(ctx, g, bases[i]); };
+  for (int i = 0; i < n; i++) {
+    auto it = ctx->frames.find(frame_ids[i]);
+    if (it != ctx->frames.end()) {   // refresh in place: from here on the gradient images are no longer this frame's
+      bases[i] = it->second.base; it->second.grad_ready = false;
+      continue;
+    }
+    if (int rc = hso_frame_alloc(ctx, g, &bases[i])) { undo(); return rc; }
+    fresh.push_back(i);
+  }
+#define HSO_BATCH_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { ctx->err = std::string(#expr) + ": " + hipGetErrorString(_e); undo(); return HSO_E_HIP; } } while (0)
+  uint8_t** d_bases = reinterpret_cast<uint8_t**>(ctx->d_batch);
+  const uint8_t** d_srcs = reinterpret_cast<const uint8_t**>(ctx->d_batch + b_ptr);
+  uint8_t** d_mids = reinterpret_cast<uint8_t**>(ctx->d_batch + 2 * b_ptr);
+  hso_frame_stats* d_stats = reinterpret_cast<hso_frame_stats*>(ctx->d_batch + 3 * b_ptr);
+  uint8_t* d_raw = reinterpret_cast<uint8_t*>(ctx->d_batch + 3 * b_ptr + b_stats);
+  uint8_t* d_mid = d_raw + b_raw;
+  HSO_BATCH_TRY(hipMemcpyAsync(d_bases, bases.data(), (size_t)n * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+  if (img_is_device) {
+    HSO_BATCH_TRY(hipMemcpyAsync(d_srcs, imgs, (size_t)n * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+  } else {
+    std::vector<const uint8_t*> staged(n);
+    for (int i = 0; i < n; i++) {
+      staged[i] = d_raw + (size_t)i * src_stride;
+      HSO_BATCH_TRY(hipMemcpyAsync(d_raw + (size_t)i * src_stride, imgs[i], src_bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    HSO_BATCH_TRY(hipMemcpyAsync(d_srcs, staged.data(), (size_t)n * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));   // staged now: `staged` may go
+  }
+  int rc;
+  if (m) {   // resize into the work area's camera-size slots, remap from there into level 0
+    std::vector<uint8_t*> mids(n);
+    for (int i = 0; i < n; i++) mids[i] = d_mid + (size_t)i * mid_stride;
+    HSO_BATCH_TRY(hipMemcpyAsync(d_mids, mids.data(), (size_t)n * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+    rc = hso_frame_resize_batch(ctx, d_srcs, src_width, src_height, d_mids, 0, width, height, n);
+    if (rc >= 0) rc = rectify_launch(ctx, *m, g, d_bases, const_cast<const uint8_t* const*>(d_mids), n);
+  } else {   // resize straight into level 0
+    rc = hso_frame_resize_batch(ctx, d_srcs, src_width, src_height, d_bases, g.off[0], width, height, n);
+  }
+  if (rc < 0) { undo(); return rc; }
+  const bool eager = ctx->opt.eager_gradients != 0;
+  rc = hso_frame_build(ctx, g, d_bases, nullptr, stats_out ? d_stats : nullptr, n, eager);
+  if (rc < 0) { undo(); return rc; }
+  if (stats_out) {
+    HSO_BATCH_TRY(hipMemcpyAsync(stats_out, d_stats, (size_t)n * sizeof(hso_frame_stats), hipMemcpyDeviceToHost, ctx->stream));
+    HSO_BATCH_TRY(hipStreamSynchronize(ctx->stream));
+  }
+#undef HSO_BATCH_TRY
+  for (int i : fresh) {   // commit
+    FrameRec rec;
+    rec.id = frame_ids[i]; rec.g = g; rec.base = bases[i];
+    ctx->frames[frame_ids[i]] = rec;
+  }
+  for (int i = 0; i < n; i++) ctx->frames[frame_ids[i]].grad_ready = eager;
+  return HSO_OK;
+}
+
 }  // extern "C"

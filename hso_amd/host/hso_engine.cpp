@@ -231,7 +231,12 @@ bool Bank::rectify_available()
   return hso_gpu_rectify_map_create && hso_gpu_rectify_map_destroy && hso_gpu_frame_upload_batch_rectified && hso_gpu_frame_download_level;
 }
 
-void Bank::set_options(bool sync_previous, bool track_no_coop, bool no_numa_pin, bool device_select, bool rectify)
+bool Bank::resize_available()
+{
+  return hso_gpu_frame_upload_batch_resized && hso_gpu_frame_download_level;
+}
+
+void Bank::set_options(bool sync_previous, bool track_no_coop, bool no_numa_pin, bool device_select, bool rectify, bool resize)
 {
   // before anything changes: the harness's `if(cam_->getUndistort())` (test/test_dataset.cpp:276) holds for a FOV camera built with
   // undistort = true and for an Equidistant camera, and for no other
@@ -247,6 +252,7 @@ void Bank::set_options(bool sync_previous, bool track_no_coop, bool no_numa_pin,
     check(hso_gpu_rectify_map_destroy(ctx_, rectify_map_), "rectification map");
     rectify_map_ = -1;
   }
+  resize_ = resize;
   sync_previous_ = sync_previous;
   no_numa_pin_ = no_numa_pin;
   device_select_ = device_select;

@@ -182,8 +182,11 @@ public:
   bool trace(int k, const char* path);
   bool trace_state(int k, bool on);
   // rectify: throws Refused for a camera the reference does not rectify; the caller checks rectify_available() first
-  void set_options(bool sync_previous, bool track_no_coop, bool no_numa_pin = false, bool device_select = false, bool rectify = false);
+  // resize: images of any one size per call are accepted from now on; the caller checks resize_available() first
+  void set_options(bool sync_previous, bool track_no_coop, bool no_numa_pin = false, bool device_select = false, bool rectify = false,
+                   bool resize = false);
   static bool rectify_available();   // the device library linked in has hso_gpu_frame_upload_batch_rectified
+  static bool resize_available();    // ... and hso_gpu_frame_upload_batch_resized
   void call_counts(int64_t* calls, int64_t* items, int cap) const;
   // algorithmic bytes (SURVEY.md section 8(d) units) of the steps so far: [frame build, tracker, matcher, pose optimiser, seeds]
   void alg_bytes(double* out, int cap) const { for (int i = 0; i < cap && i < 5; i++) out[i] = alg_bytes_[i]; }
@@ -294,6 +297,7 @@ private:
   Pinned<hso_keypoint> det_sel_;                // ... and, with device_select_, the selected keys instead
   Pinned<float> det_occ_;
   bool device_select_ = false;                  // hso_vo_options.device_select
+  bool resize_ = false;                         // hso_vo_options.resize: images of another size than the camera's are resized in the upload
   int rectify_map_ = -1;                        // hso_vo_options.rectify: the camera's rectification map on the device, -1 = images arrive rectified
   int det_corner_cap_ = 8192;                   // corners per (frame, level) the lists hold; grows when a frame has more
 };

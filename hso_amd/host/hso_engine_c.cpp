@@ -70,7 +70,12 @@ static int set_opts(Bank* b, const hso_vo_options* o)
     if (!b->poisoned) b->err = "set_options: the device library has no rectification entries (hso_gpu_frame_upload_batch_rectified)";
     return HSO_E_UNSUPPORTED;
   }
-  return guarded(b, [&]() { b->set_options(o->sync_previous != 0, o->track_no_coop != 0, no_pin, device_select, rectify); });
+  const bool resize = o->size >= 28 && o->resize != 0;
+  if (resize && !Bank::resize_available()) {     // nothing was touched
+    if (!b->poisoned) b->err = "set_options: the device library has no batched resize entry (hso_gpu_frame_upload_batch_resized)";
+    return HSO_E_UNSUPPORTED;
+  }
+  return guarded(b, [&]() { b->set_options(o->sync_previous != 0, o->track_no_coop != 0, no_pin, device_select, rectify, resize); });
 }
 int hso_vo_set_options(hso_vo* v, const hso_vo_options* o) { return v ? set_opts(v->bank, o) : HSO_E_INVALID; }
 int hso_vo_trace_state(hso_vo* v, int on) { return (v && v->bank->trace_state(0, on != 0)) ? HSO_OK : HSO_E_INVALID; }

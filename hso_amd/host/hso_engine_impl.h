@@ -22,6 +22,9 @@ extern "C" int hso_gpu_rectify_map_create(hso_gpu_ctx* ctx, const hso_camera* ca
 extern "C" int hso_gpu_rectify_map_destroy(hso_gpu_ctx* ctx, int32_t map) __attribute__((weak));
 extern "C" int hso_gpu_frame_upload_batch_rectified(hso_gpu_ctx* ctx, const int64_t* frame_ids, const uint8_t* const* imgs, int n, int32_t map,
                                                     int img_is_device, hso_frame_stats* stats_out) __attribute__((weak));
+extern "C" int hso_gpu_frame_upload_batch_resized(hso_gpu_ctx* ctx, const int64_t* frame_ids, const uint8_t* const* imgs, int n, int src_width,
+                                                  int src_height, int width, int height, int32_t rectify_map, int img_is_device,
+                                                  hso_frame_stats* stats_out) __attribute__((weak));   // hso_vo_options.resize, the same way
 extern "C" int hso_gpu_frame_download_level(hso_gpu_ctx* ctx, int64_t frame_id, int level, uint8_t* out, int* w_out, int* h_out) __attribute__((weak));
 
 namespace hso {

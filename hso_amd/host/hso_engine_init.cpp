@@ -12,7 +12,7 @@ namespace engine {
 void Bank::set_first_frames(const uint8_t* const* imgs, int w, int h, const double* stamps, const float* const* depth_z, const hso_se3* T_f_w)
 {
   previous_collect();
-  if (w != cam_.width() || h != cam_.height())
+  if (resize_ ? (w <= 0 || h <= 0) : (w != cam_.width() || h != cam_.height()))
     throw Refused("Frame: provided image has not the same size as the camera model or image is not grayscale");
   for (int k = 0; k < size(); k++) if (imgs[k] && (!depth_z || !depth_z[k])) throw Refused("set_first_frame: no depth image");   // before anything is touched
   std::vector<int> who;
@@ -29,6 +29,7 @@ void Bank::set_first_frames(const uint8_t* const* imgs, int w, int h, const doub
   release_queued();
   if (who.empty()) return;
   upload(who, imgs, w, h, stamps);
+  const int cw = cam_.width(), ch = cam_.height();
   // the detector of the initialisation (2000 features, FAST-12 hole filling), then one point per feature whose depth is known —
   // what the two-view initialisation leaves behind for its inliers
   std::vector<std::vector<hso_keypoint>> keys(who.size()), sel;
@@ -52,7 +53,7 @@ void Bank::set_first_frames(const uint8_t* const* imgs, int w, int h, const doub
     for (const hso_keypoint& kp : sel[i]) {
       Feat ft = feature_from_key(kp, s.cur);
       const int x = (int)ft.px[0], y = (int)ft.px[1];
-      const float z = (x >= 0 && y >= 0 && x < w && y < h) ? depth[(size_t)y * w + x] : 0.f;
+      const float z = (x >= 0 && y >= 0 && x < cw && y < ch) ? depth[(size_t)y * cw + x] : 0.f;   // Frame pixels: the camera's size
       if (!(z > 0)) continue;
       C.loose.push_back(ft);
       dist_of.push_back((double)z / ft.f[2]);                     // the point on the bearing whose depth along the optical axis is z

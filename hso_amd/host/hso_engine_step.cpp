@@ -31,7 +31,8 @@ struct Clock {
 // ------------------------------------------------------------------------------------------------ entry points
 void Bank::add_images(const uint8_t* const* imgs, int w, int h, const double* stamps, bool on_device)
 {
-  if (w != cam_.width() || h != cam_.height())      // src/frame.cpp:85-86: thrown before anything is touched
+  // src/frame.cpp:85-86: thrown before anything is touched.  hso_vo_options.resize: any one size, the upload resizes
+  if (resize_ ? (w <= 0 || h <= 0) : (w != cam_.width() || h != cam_.height()))
     throw Refused("Frame: provided image has not the same size as the camera model or image is not grayscale");
   if (on_device) for (int k = 0; k < size(); k++) if (imgs[k] && seq_[k]->trace.on()) throw Refused("trace: images must be host images");
   step(imgs, w, h, stamps, on_device);
@@ -153,7 +154,13 @@ void Bank::upload(const std::vector<int>& who, const uint8_t* const* imgs, int w
   }
   std::vector<hso_frame_stats> st(who.size());
   // hso_vo_options.rectify: the images are raw, `cam_->undistortImage(image, image)` (test/test_dataset.cpp:276) runs in the same call
-  if (rectify_map_ >= 0)
+  // hso_vo_options.resize: sensor-size images, ImageReader::readImage's cv::resize (src/ImageReader.cpp:79) runs in front of it
+  const int cw = cam_.width(), ch = cam_.height();
+  const bool resized = resize_ && (w != cw || h != ch);
+  if (resized)
+    check(hso_gpu_frame_upload_batch_resized(ctx_, ids.data(), ptr.data(), (int)who.size(), w, h, cw, ch, rectify_map_, on_device ? 1 : 0, st.data()),
+          "Frame (resized)");
+  else if (rectify_map_ >= 0)
     check(hso_gpu_frame_upload_batch_rectified(ctx_, ids.data(), ptr.data(), (int)who.size(), rectify_map_, on_device ? 1 : 0, st.data()), "Frame (rectified)");
   else
     check(hso_gpu_frame_upload_batch(ctx_, ids.data(), ptr.data(), (int)who.size(), w, h, on_device ? 1 : 0, st.data()), "Frame");
@@ -164,17 +171,17 @@ void Bank::upload(const std::vector<int>& who, const uint8_t* const* imgs, int w
     Frame& F = s.frames[s.cur];
     F.integral = st[i].integral_image; F.grad_mean = st[i].grad_mean;
     if (s.trace.on()) {
-      // the record holds what the Frame was built from — with rectify, level 0 as the device made it — so that a replay through
-      // hso_gpu_frame_upload reproduces the frame
+      // the record holds what the Frame was built from — with rectify or resize, level 0 as the device made it — so that a replay
+      // through hso_gpu_frame_upload reproduces the frame
       const uint8_t* img = imgs[who[i]];
-      if (rectify_map_ >= 0) {
-        rectified.resize((size_t)w * h);
+      if (rectify_map_ >= 0 || resized) {
+        rectified.resize((size_t)cw * ch);
         check(hso_gpu_frame_download_level(ctx_, F.dev_id, 0, rectified.data(), nullptr, nullptr), "trace");
         img = rectified.data();
       }
       s.trace.begin("frame_upload", 5);
-      s.trace.scalar("frame_id", (double)F.dev_id); s.trace.scalar("width", w); s.trace.scalar("height", h);
-      s.trace.field("img", img, (size_t)w * h); s.trace.field("stats", &st[i], sizeof(st[i]));
+      s.trace.scalar("frame_id", (double)F.dev_id); s.trace.scalar("width", cw); s.trace.scalar("height", ch);
+      s.trace.field("img", img, (size_t)cw * ch); s.trace.field("stats", &st[i], sizeof(st[i]));
     }
   }
 }

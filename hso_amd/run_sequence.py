@@ -2,9 +2,10 @@
 
 The reference's test_dataset harness (test/test_dataset.cpp:260-335: BenchmarkNode::runFromFolder +
 saveResult) without OpenCV: read the calibration (incl. the > 848x800 downscale rule), list the images of the
-folder, resize every image to the camera size on the device when the sensor is larger, rectify it on the device when the
-camera asks for it (`if(cam_->getUndistort()) cam_->undistortImage(image, image)`, test_dataset.cpp:276: a FOV file whose third
-line is `true`, any Equidistant file), feed FrameHandlerMono::addImage in order, write the keyframe trajectory in the reference's
+folder, hand the engine sensor-size images — it resizes them to the camera size on the device when the sensor is larger
+(hso_vo_options.resize) and rectifies them on the device when the camera asks for it (hso_vo_options.rectify;
+`if(cam_->getUndistort()) cam_->undistortImage(image, image)`, test_dataset.cpp:276: a FOV file whose third line is `true`, any
+Equidistant file) —, feed FrameHandlerMono::addImage in order, write the keyframe trajectory in the reference's
 format.
 
 Options (the reference's `key=value` style, test_dataset.cpp:66-114):
@@ -49,21 +50,28 @@ def main(argv, return_line=False):
     if "depth0" in opt:
         d0 = np.load(opt["depth0"]) if opt["depth0"].endswith(".npy") else np.fromfile(opt["depth0"], np.float32).reshape(H, W)
     odo = vo.VisualOdometry(cam, int(opt.get("max_fts", 200)))
-    if calib["undistort"]:
-        # cam_->undistortImage between readImage and addImage (test/test_dataset.cpp:276): the engine takes raw camera-size images
-        # and rectifies them in its upload (hso_vo_options.rectify); depth0, when given, is in rectified geometry
-        odo.set_options(rectify=True)
+    # ImageReader::readImage's cv::resize to the camera size (src/ImageReader.cpp:79) and cam_->undistortImage between readImage and
+    # addImage (test/test_dataset.cpp:276) both run in the engine's upload: it takes sensor-size raw images (hso_vo_options.resize,
+    # .rectify); depth0, when given, is in the camera's size and rectified geometry
+    first = load_image(files[start]) if start < end else None
+    want_resize = first is not None and first.shape != (H, W)
+    resize_ctx = None
+    if calib["undistort"] or want_resize:
+        try:
+            odo.set_options(rectify=bool(calib["undistort"]), resize=want_resize)
+        except capi.HsoGpuError as e:
+            if not want_resize or "(%d)" % capi.E_UNSUPPORTED not in str(e):
+                raise
+            # a device library without the batched resize entry: resize through a context of our own and hand over camera-size images
+            resize_ctx = capi.Context(0)
+            if calib["undistort"]:
+                odo.set_options(rectify=True)
     if "trace" in opt:
         odo.trace(opt["trace"])
-    resize_ctx = None
 
     def prepare(img):
-        # ImageReader::readImage: cv::resize to the camera size (src/ImageReader.cpp:79), on the device
-        nonlocal resize_ctx
-        if img.shape == (H, W):
+        if resize_ctx is None or img.shape == (H, W):
             return img
-        if resize_ctx is None:
-            resize_ctx = capi.Context(0)
         resize_ctx.frame_upload_resized(1, img, W, H)
         out = resize_ctx.frame_level(1, 0, W, H)
         resize_ctx.frame_release(1)
@@ -74,7 +82,7 @@ def main(argv, return_line=False):
         odo.start()                                     # vo_->start(), test/test_dataset.cpp:276
     trace_frames = int(opt.get("trace_frames", 0))
     for k, i in enumerate(range(start, end)):
-        img = prepare(load_image(files[i]))
+        img = prepare(first if k == 0 else load_image(files[i]))
         if trace_frames and k == trace_frames:
             odo.trace(None)
         t0 = time.perf_counter()

@@ -25,9 +25,9 @@ class VoStatus(C.Structure):
 
 
 class VoOptions(C.Structure):
-    # hso_vo_options (include/hso_vo.h).  The header names the word after device_select `rectify` and keeps two reserved words behind
-    # it; the binding keeps the three words as one array — its layout is pinned by tests/test_device_select_cpu.py — and names the
-    # first through a property.
+    # hso_vo_options (include/hso_vo.h).  The header names the words after device_select `rectify` and `resize` and keeps one
+    # reserved word behind them; the binding keeps the three words as one array — its layout is pinned by
+    # tests/test_device_select_cpu.py — and names the first two through properties.
     _fields_ = [("size", C.c_int32), ("sync_previous", C.c_int32), ("track_no_coop", C.c_int32), ("no_numa_pin", C.c_int32), ("device_select", C.c_int32),
                 ("reserved", C.c_int32 * 3)]
 
@@ -38,6 +38,14 @@ class VoOptions(C.Structure):
     @rectify.setter
     def rectify(self, v):
         self.reserved[0] = int(v)
+
+    @property
+    def resize(self):
+        return self.reserved[1]
+
+    @resize.setter
+    def resize(self, v):
+        self.reserved[1] = int(v)
 
 
 _lib = None
@@ -150,10 +158,13 @@ class MultiVisualOdometry:
     def trace(self, k, path):
         self._check(self.lib.hso_vo_multi_trace(self.h, int(k), path.encode() if path else None), "trace")
 
-    def set_options(self, sync_previous=False, track_no_coop=False, no_numa_pin=False, device_select=False, rectify=False):
-        """rectify: the images handed over from now on are raw and the engine rectifies them on the device (hso_vo_options.rectify)"""
+    def set_options(self, sync_previous=False, track_no_coop=False, no_numa_pin=False, device_select=False, rectify=False, resize=False):
+        """rectify: the images handed over from now on are raw and the engine rectifies them on the device (hso_vo_options.rectify).
+        resize: they may have any one size per call (sensor images); the engine resizes them to the camera's size on the device, in
+        front of the rectification (hso_vo_options.resize).  depth images stay camera-size."""
         o = VoOptions(C.sizeof(VoOptions), int(bool(sync_previous)), int(bool(track_no_coop)), int(bool(no_numa_pin)), int(bool(device_select)))
         o.rectify = int(bool(rectify))
+        o.resize = int(bool(resize))
         self._check(self.lib.hso_vo_multi_set_options(self.h, C.byref(o)), "set_options")
 
     def start(self, which=None):
@@ -240,16 +251,20 @@ class VisualOdometry:
         self._check(self.lib.hso_vo_trace_state(self.h, 1 if state else 0), "trace_state")
         self._check(self.lib.hso_vo_trace(self.h, path.encode() if path else None), "trace")
 
-    def set_options(self, sync_previous=False, track_no_coop=False, no_numa_pin=False, device_select=False, rectify=False):
-        """rectify: the images handed over from now on are raw and the engine rectifies them on the device (hso_vo_options.rectify)"""
+    def set_options(self, sync_previous=False, track_no_coop=False, no_numa_pin=False, device_select=False, rectify=False, resize=False):
+        """rectify: the images handed over from now on are raw and the engine rectifies them on the device (hso_vo_options.rectify).
+        resize: they may have any one size per call (sensor images); the engine resizes them to the camera's size on the device, in
+        front of the rectification (hso_vo_options.resize).  depth images stay camera-size."""
         o = VoOptions(C.sizeof(VoOptions), int(bool(sync_previous)), int(bool(track_no_coop)), int(bool(no_numa_pin)), int(bool(device_select)))
         o.rectify = int(bool(rectify))
+        o.resize = int(bool(resize))
         self._check(self.lib.hso_vo_set_options(self.h, C.byref(o)), "set_options")
 
     def set_first_frame(self, img, depth_z, timestamp=0.0, T_f_w=None):
         img = np.ascontiguousarray(img, np.uint8)
         depth_z = np.ascontiguousarray(depth_z, np.float32)
-        assert depth_z.shape == img.shape
+        # the depth image is indexed by Frame pixels: the camera's size when the engine resizes the image (hso_vo_options.resize)
+        assert depth_z.shape == img.shape or depth_z.shape == (self.cam.height, self.cam.width)
         self._check(self.lib.hso_vo_set_first_frame(self.h, capi._ptr(img), img.shape[1], img.shape[0], float(timestamp),
                                                     capi._ptr(depth_z), C.byref(T_f_w) if T_f_w is not None else None),
                     "set_first_frame")

@@ -194,6 +194,19 @@ int hso_gpu_frame_upload_rectified(hso_gpu_ctx* ctx, int64_t frame_id, const uin
  * when a resident frame has another size than the map. */
 int hso_gpu_frame_upload_batch_rectified(hso_gpu_ctx* ctx, const int64_t* frame_ids, const uint8_t* const* imgs, int n, int32_t map,
                                          int img_is_device, hso_frame_stats* stats_out /* n or NULL */);
+/* hso_gpu_frame_upload_batch for sensor-size images: ImageReader::readImage's cv::resize(image, image, m_img_new_size)
+ * (src/ImageReader.cpp:79; INTER_LINEAR, CV_8UC1, the bytes of hso_gpu_frame_upload_resized) of n images of src_width x src_height
+ * to width x height in one launch, then — rectify_map >= 0 — the remap of hso_gpu_frame_upload_batch_rectified through a map of
+ * exactly width x height (resize first, then undistortImage, as test/test_dataset.cpp:275-276 does), then the batched build.
+ * Without a map the resize writes the frames' level-0 planes directly.  Same contract as the two batched entries: a resident id
+ * is refreshed in place, nothing new is resident after an error, asynchronous with device images and stats_out == NULL.  With
+ * src size == destination size it IS those entries.  Host images are staged in the context's work area, which holds n source
+ * images and, when rectifying, n images of the destination size: HSO_E_NOMEM (nothing changed) when it cannot be had.
+ * HSO_E_INVALID: null arguments, n <= 0, a non-positive source size, width % 4 != 0, a destination smaller than 64x64, an unknown
+ * map or one of another size than the destination, a new id that appears twice, a resident frame of another size. */
+int hso_gpu_frame_upload_batch_resized(hso_gpu_ctx* ctx, const int64_t* frame_ids, const uint8_t* const* imgs, int n,
+                                       int src_width, int src_height, int width, int height, int32_t rectify_map /* -1: none */,
+                                       int img_is_device, hso_frame_stats* stats_out /* n or NULL */);
 
 int hso_gpu_frame_release(hso_gpu_ctx* ctx, int64_t frame_id);
 /* n frames with one wait for the stream (~Frame of the frames n sequences dropped in a step); all or nothing: HSO_E_NOFRAME /

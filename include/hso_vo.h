@@ -56,7 +56,15 @@ typedef struct hso_vo_options {
                                  A recorded sequence's frame_upload records hold the rectified image.  hso_vo_set_options returns
                                  HSO_E_INVALID for a camera the reference does not rectify (pinhole; FOV with undistort = false) and
                                  HSO_E_UNSUPPORTED when the device library lacks the entries; set it before the first frame */
-  int32_t reserved[2];
+  int32_t resize;             /* 1: the images handed to the same calls may have any width x height (one size per call, device pointers
+                                 included): sensor-size images, and the engine runs ImageReader::readImage's cv::resize(image, image,
+                                 m_img_new_size) (src/ImageReader.cpp:79) to the camera's size on the device, in the upload
+                                 (hso_gpu_frame_upload_batch_resized) and in front of the rectification when `rectify` is set too, as the
+                                 harness orders them.  Images of exactly the camera's size take the path they take without the option.
+                                 depth_z stays indexed by the pixels of the Frame (the camera's size).  A recorded sequence's frame_upload
+                                 records hold the resized image.  0: an image of another size is refused.  hso_vo_set_options returns
+                                 HSO_E_UNSUPPORTED when the device library lacks the entry; set it before the first frame */
+  int32_t reserved[1];
 } hso_vo_options;
 int hso_vo_set_options(hso_vo* vo, const hso_vo_options* options);
 /* first keyframe: features are detected the way the initialisation detects them and every feature with
