@@ -54,6 +54,7 @@ class KltParams(C.Structure):
 
 
 KLT_RESULT_DTYPE = np.dtype([("px", np.float32, 2), ("ncc", np.float32), ("status", np.int32)])
+KLT_PAIR_DTYPE = np.dtype([("frame_prev", np.int64), ("frame_cur", np.int64), ("first", np.int32), ("n", np.int32)])   # hso_klt_pair
 KLT_TRACKED, KLT_PATCH_OK = 1, 2
 
 
@@ -357,6 +358,7 @@ def load():
     lib.hso_gpu_host_alloc.argtypes = [vp, C.c_size_t, P(vp)]
     lib.hso_gpu_host_free.argtypes = [vp, vp]
     lib.hso_gpu_klt_track.argtypes = [vp, i64, i64, vp, vp, i32, P(KltParams), vp]
+    lib.hso_gpu_klt_track_multi.argtypes = [vp, vp, i32, vp, vp, i32, P(KltParams), vp]
     lib.hso_gpu_klt_levels.argtypes = [i32, i32, i32, i32]
     lib.hso_gpu_klt_debug_level.argtypes = [vp, i64, i32, vp, vp]
     lib.hso_gpu_seed_activate_multi.argtypes = [vp, P(Camera), P(Seed), i32, P(i32), P(ActivateTarget), P(i32), P(ActivateOut),
@@ -423,7 +425,7 @@ EXPORTED_SYMBOLS = [
     "hso_gpu_select_octree_batch", "hso_gpu_detect_select_multi",
     "hso_gpu_rectify_build_map", "hso_gpu_rectify_host", "hso_gpu_rectify_map_create", "hso_gpu_rectify_map_create_tables",
     "hso_gpu_rectify_map_destroy", "hso_gpu_frame_upload_rectified", "hso_gpu_frame_upload_batch_rectified",
-    "hso_gpu_frame_upload_batch_resized",
+    "hso_gpu_frame_upload_batch_resized", "hso_gpu_klt_track_multi",
 ]
 
 
@@ -1056,6 +1058,22 @@ class Context:
         out = np.zeros(len(a), KLT_RESULT_DTYPE)
         params = params or KltParams()
         self._check(self.lib.hso_gpu_klt_track(self.h, frame_prev, frame_cur, _ptr(a), _ptr(b), len(a), C.byref(params), _ptr(out)), "klt_track")
+        return out
+
+    def klt_track_multi(self, pairs, px_prev, px_init, params=None):
+        """hso_gpu_klt_track_multi: pairs = [(frame_prev, frame_cur, first, n), ...] over the concatenated tables px_prev / px_init
+        (n_total x 2) -> KLT_RESULT_DTYPE array of n_total rows (rows no pair owns come back zero)."""
+        a = np.ascontiguousarray(px_prev, np.float32).reshape(-1, 2)
+        b = np.ascontiguousarray(px_init, np.float32).reshape(-1, 2)
+        if len(a) != len(b):
+            raise ValueError("klt_track_multi: px_prev and px_init differ in length")
+        tab = np.zeros(len(pairs), KLT_PAIR_DTYPE)
+        for i, (fp, fc, first, n) in enumerate(pairs):
+            tab[i] = (fp, fc, first, n)
+        out = np.zeros(len(a), KLT_RESULT_DTYPE)
+        params = params or KltParams()
+        self._check(self.lib.hso_gpu_klt_track_multi(self.h, _ptr(tab) if len(tab) else None, len(tab), _ptr(a), _ptr(b), len(a), C.byref(params), _ptr(out)),
+                    "klt_track_multi")
         return out
 
     def klt_debug_level(self, frame, level, width, height):

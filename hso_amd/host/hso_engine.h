@@ -199,6 +199,7 @@ private:
   // phases of a step (device calls on the caller's thread; per-sequence work through par() / the pool)
   void upload(const std::vector<int>& who, const uint8_t* const* imgs, int w, int h, const double* stamps, bool on_device = false);
   void initialise(const std::vector<int>& who);
+  void second_frame(int k, const hso_klt_result* res, size_t n);   // addSecondFrame behind the KLT call (pool thread)
   void chain(const std::vector<int>& who);
   void track_group(const std::vector<int>& who, const std::vector<Id>& ref, const std::vector<Id>& cur, const hso_track_params& p);
   void prepare_job(int k, hso_seq_job& job, std::vector<int32_t>& temps);

@@ -26,6 +26,10 @@ extern "C" int hso_gpu_frame_upload_batch_resized(hso_gpu_ctx* ctx, const int64_
                                                   int src_height, int width, int height, int32_t rectify_map, int img_is_device,
                                                   hso_frame_stats* stats_out) __attribute__((weak));   // hso_vo_options.resize, the same way
 extern "C" int hso_gpu_frame_download_level(hso_gpu_ctx* ctx, int64_t frame_id, int level, uint8_t* out, int* w_out, int* h_out) __attribute__((weak));
+// the two-view initialisation's KLT for all starting sequences in one call; without it (tests/fakegpu) Bank::initialise makes one
+// hso_gpu_klt_track call per sequence
+extern "C" int hso_gpu_klt_track_multi(hso_gpu_ctx* ctx, const hso_klt_pair* pairs, int n_pairs, const float* px_prev, const float* px_init, int n_total,
+                                       const hso_klt_params* params, hso_klt_result* out) __attribute__((weak));
 
 namespace hso {
 namespace engine {

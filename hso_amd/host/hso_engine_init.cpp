@@ -4,6 +4,7 @@
 // of the chained reprojection call.
 #include "hso_engine_impl.h"
 #include "hso_init.h"
+#include "hso_klt_batch.h"
 
 namespace hso {
 namespace engine {
@@ -161,95 +162,132 @@ void Bank::initialise(const std::vector<int>& who)
       s.outcome = kKeyframe;
     }
   }
+  if (second.empty()) return;
+  // KltHomographyInit::addSecondFrame in three phases.  (1) the point tables of all these sequences, concatenated; (2) KLT from
+  // each sequence's previous frame: ONE device call for all of them (a device library without the batched entry — tests/fakegpu —
+  // gets one call per sequence over the same tables); (3) what the reference does with the tracked points, per sequence on the
+  // pool.  Nothing in (3) looks beyond its own sequence: the two estimators seed their samplers per call (hso_init.cpp: Lcg) and
+  // keep no state, so which thread runs a sequence cannot matter; the frames a sequence lets go are noted in its StepData and
+  // queued for release afterwards, in sequence order.
+  KltBatch B;
   for (int k : second) {
-    // KltHomographyInit::addSecondFrame: KLT from the previous frame (one device call per sequence: a handful per run)
     Seq& s = *seq_[k];
-    TwoView& I = s.init;
-    Frame& C = s.frames[s.cur];
     s.log = hso_vo_status{};
-    const size_t n = I.px_cur.size();
-    std::vector<float> a(2 * n), b(2 * n);
-    // px_prev_ = the positions in the previous frame; while only the reference has been seen both are the reference's
-    for (size_t i = 0; i < n; i++) { a[2 * i] = (float)I.px_cur[i][0]; a[2 * i + 1] = (float)I.px_cur[i][1]; b[2 * i] = a[2 * i]; b[2 * i + 1] = a[2 * i + 1]; }
-    std::vector<hso_klt_result> res(n);
-    hso_klt_params kp{};
-    kp.win_size = 30; kp.max_level = 4; kp.max_iter = 30; kp.use_initial_flow = 1; kp.epsilon = 0.0001;
-    check(hso_gpu_klt_track(ctx_, s.frames[I.prev].dev_id, C.dev_id, a.data(), b.data(), (int)n, &kp, res.data()), "trackKlt");
-    n_calls_[9]++; n_items_[9]++;
-    if (s.trace.on()) {
-      Trace& t = s.trace;
-      t.begin("klt_track", 6);
-      t.scalar("prev_frame_id", (double)s.frames[I.prev].dev_id); t.scalar("cur_frame_id", (double)C.dev_id);
-      t.field("px_prev", a.data(), sizeof(float) * a.size()); t.field("px_init", b.data(), sizeof(float) * b.size());
-      t.field("params", &kp, sizeof(kp)); t.field("result", res.data(), sizeof(hso_klt_result) * n);
-    }
-    std::vector<double> disparity;
-    {
-      TwoView K;
-      for (size_t i = 0; i < n; i++) {
-        if ((res[i].status & (HSO_KLT_TRACKED | HSO_KLT_PATCH_OK)) != (HSO_KLT_TRACKED | HSO_KLT_PATCH_OK)) continue;
-        const Vector2d pc = {(double)res[i].px[0], (double)res[i].px[1]};
-        K.px_ref.push_back(I.px_ref[i]); K.px_cur.push_back(pc); K.f_ref.push_back(I.f_ref[i]); K.kind.push_back(I.kind[i]);
-        K.f_cur.push_back(cam_.cam2world(pc));
-        disparity.push_back(std::hypot(I.px_ref[i][0] - pc[0], I.px_ref[i][1] - pc[1]));
-      }
-      I.px_ref.swap(K.px_ref); I.px_cur.swap(K.px_cur); I.f_ref.swap(K.f_ref); I.f_cur.swap(K.f_cur); I.kind.swap(K.kind);
-    }
-    { const Id old = I.prev; I.prev = s.cur; s.hold(s.cur); release_frame(s, old); }
-    if ((int)disparity.size() < cfg_.init_min_tracked) { s.outcome = kFailure; continue; }
-    { std::vector<double> dd = disparity; if (upper_median(dd) < cfg_.init_min_disparity) { s.outcome = kNoKeyframe; continue; } }
-    std::vector<int> inliers; std::vector<Vector3d> xyz; SE3 T_cur_ref; int used_h = 0;
-    initialization::computeInitializeMatrix(I.f_ref, I.f_cur, cam_.errorMultiplier2(), cfg_.poseoptim_thresh, inliers, xyz, T_cur_ref, &used_h);
-    if ((int)inliers.size() < cfg_.init_min_inliers) { s.outcome = kFailure; continue; }
-    // the map is rescaled so that the median depth of the triangulated points equals map_scale (:97-104)
-    std::vector<double> depths;
-    for (const Vector3d& p : xyz) depths.push_back(p[2]);
-    const double scale = cfg_.map_scale / upper_median(depths);
-    Frame& R = s.frames[I.ref];
-    C.T = T_cur_ref * R.T;
-    {
-      const Vector3d pr = s.centre(R), pc = s.centre(C);
-      const Vector3d moved = {pr[0] + (pc[0] - pr[0]) * scale, pr[1] + (pc[1] - pr[1]) * scale, pr[2] + (pc[2] - pr[2]) * scale};
-      SE3 rot = C.T; rot.v.t[0] = rot.v.t[1] = rot.v.t[2] = 0;
-      const Vector3d t = rot * moved;
-      C.T.v.t[0] = -t[0]; C.T.v.t[1] = -t[1]; C.T.v.t[2] = -t[2];
-    }
-    const SE3 T_w_cur = C.T.inverse();
-    C.loose.clear();
-    for (int id : inliers) {                                      // one point per inlier, observed in both frames (:110-170)
-      const Vector2d pc = I.px_cur[id], pr = I.px_ref[id];
-      if (!(inside(cam_, (int)pc[0], (int)pc[1], 10) && inside(cam_, (int)pr[0], (int)pr[1], 10) && xyz[id][2] > 0)) continue;
-      const Vector3d pos = T_w_cur * Vector3d{xyz[id][0] * scale, xyz[id][1] * scale, xyz[id][2] * scale};
-      const std::array<double, 3>& kind = I.kind[id];
-      Feat in_ref, in_cur;
-      in_ref.frame = I.ref; in_cur.frame = s.cur;
-      in_ref.px[0] = pr[0]; in_ref.px[1] = pr[1]; in_cur.px[0] = pc[0]; in_cur.px[1] = pc[1];
-      in_ref.type = in_cur.type = kind[2] == 0 ? HSO_FTR_CORNER : kind[2] == 1 ? HSO_FTR_EDGELET : HSO_FTR_GRADIENT;
-      Vector3d fr = I.f_ref[id], fc = I.f_cur[id];
-      if (in_ref.type == HSO_FTR_GRADIENT) { fr = cam_.cam2world(pr); fc = cam_.cam2world(pc); }
-      if (in_ref.type == HSO_FTR_EDGELET) { in_ref.grad[0] = in_cur.grad[0] = kind[0]; in_ref.grad[1] = in_cur.grad[1] = kind[1]; }
-      for (int c = 0; c < 3; c++) { in_ref.f[c] = fr[c]; in_cur.f[c] = fc[c]; }
-      s.feats.push_back(in_ref);
-      const Id f = (Id)s.feats.size() - 1;
-      R.fts.push_back(f);
-      s.list_grew(I.ref);
-      const double pn[3] = {pos[0], pos[1], pos[2]};
-      const Id p = s.new_point(pos, f, 1.0 / len3(pn), kPtUnknown);   // as written (:124): the reference frame sits at the origin
-      s.feats[f].point = p;
-      s.observe(p, f);
-      in_cur.point = p;
-      C.loose.push_back(in_cur);
-    }
-    release_frame(s, I.ref); release_frame(s, I.prev);
-    I.clear();
-    s.stage = kRunning;
-    s.after_init = true;
-    s.refresh_keys(R);                                            // firstFrame_->setKeyPoints()
-    s.outcome = kKeyframe;
-    s.log.n_matches = (int)C.loose.size();
-    C.n_fts = (int32_t)C.loose.size();
-    C.n_inliers = 0;
+    B.add(s.frames[s.init.prev].dev_id, s.frames[s.cur].dev_id, s.init.px_cur, s.init.px_cur.size());
   }
+  B.finish();
+  hso_klt_params kp{};
+  kp.win_size = 30; kp.max_level = 4; kp.max_iter = 30; kp.use_initial_flow = 1; kp.epsilon = 0.0001;
+  {
+    Sub t(this, "init: klt");
+    if (hso_gpu_klt_track_multi) {
+      check(hso_gpu_klt_track_multi(ctx_, B.pairs.data(), (int)B.pairs.size(), B.px_prev.data(), B.px_init.data(), B.n_total(), &kp, B.res.data()), "trackKlt");
+      n_calls_[9]++; n_items_[9] += (int64_t)B.pairs.size();
+    } else {
+      for (int p = 0; p < (int)B.pairs.size(); p++) {
+        check(hso_gpu_klt_track(ctx_, B.pairs[(size_t)p].frame_prev, B.pairs[(size_t)p].frame_cur, B.prev_of(p), B.init_of(p), (int)B.rows(p), &kp, B.res_of(p)), "trackKlt");
+        n_calls_[9]++; n_items_[9]++;
+      }
+    }
+  }
+  for (size_t i = 0; i < second.size(); i++) {
+    // a traced sequence's record is the single call's, cut from the batch's tables: hso_gpu_klt_track replays it
+    Seq& s = *seq_[second[i]];
+    if (!s.trace.on()) continue;
+    const int p = (int)i;
+    Trace& t = s.trace;
+    t.begin("klt_track", 6);
+    t.scalar("prev_frame_id", (double)B.pairs[i].frame_prev); t.scalar("cur_frame_id", (double)B.pairs[i].frame_cur);
+    t.field("px_prev", B.prev_of(p), sizeof(float) * 2 * B.rows(p)); t.field("px_init", B.init_of(p), sizeof(float) * 2 * B.rows(p));
+    t.field("params", &kp, sizeof(kp)); t.field("result", B.res_of(p), sizeof(hso_klt_result) * B.rows(p));
+  }
+  std::vector<int> slot_of((size_t)size(), -1);
+  for (size_t i = 0; i < second.size(); i++) slot_of[(size_t)second[i]] = (int)i;
+  {
+    Sub t(this, "init: geometry");
+    par(second, [&](int k) { second_frame(k, B.res_of(slot_of[(size_t)k]), B.rows(slot_of[(size_t)k])); });
+  }
+  for (int k : second) {
+    StepData& d = *step_[k];
+    to_release_.insert(to_release_.end(), d.released.begin(), d.released.end());
+    d.released.clear();
+  }
+}
+
+// the rest of KltHomographyInit::addSecondFrame for sequence k, given its KLT results: runs on a pool thread and touches nothing
+// outside the sequence and its StepData
+void Bank::second_frame(int k, const hso_klt_result* res, size_t n)
+{
+  Seq& s = *seq_[k];
+  StepData& d = *step_[k];
+  TwoView& I = s.init;
+  Frame& C = s.frames[s.cur];
+  std::vector<double> disparity;
+  {
+    TwoView K;
+    for (size_t i = 0; i < n; i++) {
+      if ((res[i].status & (HSO_KLT_TRACKED | HSO_KLT_PATCH_OK)) != (HSO_KLT_TRACKED | HSO_KLT_PATCH_OK)) continue;
+      const Vector2d pc = {(double)res[i].px[0], (double)res[i].px[1]};
+      K.px_ref.push_back(I.px_ref[i]); K.px_cur.push_back(pc); K.f_ref.push_back(I.f_ref[i]); K.kind.push_back(I.kind[i]);
+      K.f_cur.push_back(cam_.cam2world(pc));
+      disparity.push_back(std::hypot(I.px_ref[i][0] - pc[0], I.px_ref[i][1] - pc[1]));
+    }
+    I.px_ref.swap(K.px_ref); I.px_cur.swap(K.px_cur); I.f_ref.swap(K.f_ref); I.f_cur.swap(K.f_cur); I.kind.swap(K.kind);
+  }
+  { const Id old = I.prev; I.prev = s.cur; s.hold(s.cur); release_frame_deferred(s, d, old); }
+  if ((int)disparity.size() < cfg_.init_min_tracked) { s.outcome = kFailure; return; }
+  { std::vector<double> dd = disparity; if (upper_median(dd) < cfg_.init_min_disparity) { s.outcome = kNoKeyframe; return; } }
+  std::vector<int> inliers; std::vector<Vector3d> xyz; SE3 T_cur_ref; int used_h = 0;
+  initialization::computeInitializeMatrix(I.f_ref, I.f_cur, cam_.errorMultiplier2(), cfg_.poseoptim_thresh, inliers, xyz, T_cur_ref, &used_h);
+  if ((int)inliers.size() < cfg_.init_min_inliers) { s.outcome = kFailure; return; }
+  // the map is rescaled so that the median depth of the triangulated points equals map_scale (:97-104)
+  std::vector<double> depths;
+  for (const Vector3d& p : xyz) depths.push_back(p[2]);
+  const double scale = cfg_.map_scale / upper_median(depths);
+  Frame& R = s.frames[I.ref];
+  C.T = T_cur_ref * R.T;
+  {
+    const Vector3d pr = s.centre(R), pc = s.centre(C);
+    const Vector3d moved = {pr[0] + (pc[0] - pr[0]) * scale, pr[1] + (pc[1] - pr[1]) * scale, pr[2] + (pc[2] - pr[2]) * scale};
+    SE3 rot = C.T; rot.v.t[0] = rot.v.t[1] = rot.v.t[2] = 0;
+    const Vector3d t = rot * moved;
+    C.T.v.t[0] = -t[0]; C.T.v.t[1] = -t[1]; C.T.v.t[2] = -t[2];
+  }
+  const SE3 T_w_cur = C.T.inverse();
+  C.loose.clear();
+  for (int id : inliers) {                                      // one point per inlier, observed in both frames (:110-170)
+    const Vector2d pc = I.px_cur[id], pr = I.px_ref[id];
+    if (!(inside(cam_, (int)pc[0], (int)pc[1], 10) && inside(cam_, (int)pr[0], (int)pr[1], 10) && xyz[id][2] > 0)) continue;
+    const Vector3d pos = T_w_cur * Vector3d{xyz[id][0] * scale, xyz[id][1] * scale, xyz[id][2] * scale};
+    const std::array<double, 3>& kind = I.kind[id];
+    Feat in_ref, in_cur;
+    in_ref.frame = I.ref; in_cur.frame = s.cur;
+    in_ref.px[0] = pr[0]; in_ref.px[1] = pr[1]; in_cur.px[0] = pc[0]; in_cur.px[1] = pc[1];
+    in_ref.type = in_cur.type = kind[2] == 0 ? HSO_FTR_CORNER : kind[2] == 1 ? HSO_FTR_EDGELET : HSO_FTR_GRADIENT;
+    Vector3d fr = I.f_ref[id], fc = I.f_cur[id];
+    if (in_ref.type == HSO_FTR_GRADIENT) { fr = cam_.cam2world(pr); fc = cam_.cam2world(pc); }
+    if (in_ref.type == HSO_FTR_EDGELET) { in_ref.grad[0] = in_cur.grad[0] = kind[0]; in_ref.grad[1] = in_cur.grad[1] = kind[1]; }
+    for (int c = 0; c < 3; c++) { in_ref.f[c] = fr[c]; in_cur.f[c] = fc[c]; }
+    s.feats.push_back(in_ref);
+    const Id f = (Id)s.feats.size() - 1;
+    R.fts.push_back(f);
+    s.list_grew(I.ref);
+    const double pn[3] = {pos[0], pos[1], pos[2]};
+    const Id p = s.new_point(pos, f, 1.0 / len3(pn), kPtUnknown);   // as written (:124): the reference frame sits at the origin
+    s.feats[f].point = p;
+    s.observe(p, f);
+    in_cur.point = p;
+    C.loose.push_back(in_cur);
+  }
+  release_frame_deferred(s, d, I.ref); release_frame_deferred(s, d, I.prev);
+  I.clear();
+  s.stage = kRunning;
+  s.after_init = true;
+  s.refresh_keys(R);                                            // firstFrame_->setKeyPoints()
+  s.outcome = kKeyframe;
+  s.log.n_matches = (int)C.loose.size();
+  C.n_fts = (int32_t)C.loose.size();
+  C.n_inliers = 0;
 }
 
 // ------------------------------------------------------------------------------------------------ trace of the chain call

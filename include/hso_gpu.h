@@ -1205,6 +1205,17 @@ typedef struct hso_klt_result {
 int hso_gpu_klt_track(hso_gpu_ctx* ctx, int64_t frame_prev, int64_t frame_cur, const float* px_prev, const float* px_init, int n,
                       const hso_klt_params* params, hso_klt_result* out);
 int hso_gpu_klt_levels(int width, int height, int win, int max_level);   /* index of the coarsest level the call above uses */
+/* The same for any number of frame pairs in ONE call (the sequences of a bank that start together: one upload, one launch per
+ * pyramid level for all pairs, one tracking launch, one download, one wait); hso_gpu_klt_track is a batch of one pair through the
+ * same code, so a point's result does not depend on what travels with it.  px_prev / px_init / out are concatenated tables of
+ * n_total rows; pair p owns rows first .. first + n - 1.  The ranges may come in any order and may leave rows unowned (their
+ * results come back all zero), n = 0 is legal, a frame may serve several pairs; all frames have one size; one `params` serves
+ * every pair.  HSO_E_INVALID: ranges that overlap or leave the tables, frames of different sizes, the window / level limits of the
+ * single call; HSO_E_NOFRAME: a frame that is not resident — all checked before anything is queued.  n_pairs = 0: HSO_OK.
+ * Work area: about 2.2 MB per pair with points at 752x480 plus 36 bytes per row (formula: hso_amd/csrc/hso_klt.hip). */
+typedef struct hso_klt_pair { int64_t frame_prev, frame_cur; int32_t first, n; } hso_klt_pair;
+int hso_gpu_klt_track_multi(hso_gpu_ctx* ctx, const hso_klt_pair* pairs, int n_pairs, const float* px_prev, const float* px_init, int n_total,
+                            const hso_klt_params* params, hso_klt_result* out);
 /* static tables of include/hso/CoarseTracker.h:58-120 for a level */
 int hso_gpu_tracker_pattern(int max_level, int level, int* patch_area,
                             int* half_patch, int8_t* offsets_xy /* 2*40 */);

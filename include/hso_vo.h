@@ -118,7 +118,9 @@ int hso_vo_multi_size(const hso_vo_multi* m);
 int hso_vo_multi_set_first_frames(hso_vo_multi* m, const uint8_t* const* imgs, int width, int height, const double* timestamps,
                                   const float* const* depth_z, const hso_se3* T_f_w /* n_sequences or NULL */);
 /* hso_vo_start for every sequence (which = NULL) or for the sequences with which[k] != 0: their next images run the two-view
- * initialisation; its KLT call has no multi-sequence form and is serialised with the other sequences' device calls */
+ * initialisation.  Per step its KLT is one hso_gpu_klt_track_multi call for all sequences in their second stage, and what
+ * follows (disparity test, model estimation, triangulation) runs per sequence on the bank's worker pool; against a device library
+ * without that entry (the CPU stand-in of the tests) the engine makes one hso_gpu_klt_track call per sequence instead */
 int hso_vo_multi_start(hso_vo_multi* m, const uint8_t* which);
 int hso_vo_multi_add_images(hso_vo_multi* m, const uint8_t* const* imgs, int width, int height, const double* timestamps);
 /* the same with images that already live in device memory (imgs[k] = device pointer to width * height bytes): a capture or
@@ -133,7 +135,8 @@ int hso_vo_multi_get_keyframes(hso_vo_multi* m, int sequence, double* timestamps
 int hso_vo_multi_get_trajectory(hso_vo_multi* m, int sequence, double* timestamps, hso_se3* T_f_w, int cap);
 /* batched C-ABI calls issued so far and the per-sequence requests they carried, per kind: [0] frame upload, [1] frame release,
  * [2] tracker, [3] reprojection + matching, [4] matching alone, [5] pose, [6] seed observation, [7] seed activation, [8] local BA,
- * [9] calls without a multi-sequence form.  Returns the number of kinds. */
+ * [9] every other call (the detector, the depth filter's previous-frame pass, the two-view initialisation's KLT: one call per
+ * step, an item per sequence in its second stage).  Returns the number of kinds. */
 int hso_vo_multi_call_counts(hso_vo_multi* m, int64_t* calls, int64_t* items, int cap);
 /* The host side of a bank is a small thread pool (per-sequence bookkeeping between the device calls).  A process that runs several
  * banks side by side (one thread each, independent sequences shard freely within a GPU too) says so BEFORE it creates them: every
