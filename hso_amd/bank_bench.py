@@ -94,7 +94,7 @@ def _gpu_busy_reader(device):
 
 
 def run_banks(n_banks, n_seq, frames, max_fts, distinct=8, spec=None, device=0, seqs=None, want_traj=False, lib_path=None, to_device=None, steady_from=None,
-              host_images=False, no_numa_pin=False, device_select=False):
+              host_images=False, no_numa_pin=False, device_select=False, ba_fused=False):
     """n_banks engines of n_seq sequences each, every one on its own host thread with its own device context / stream: the
     device work of one bank overlaps the bookkeeping and the PCIe traffic of the others (independent sequences shard freely, also
     within one GPU).  Whole-run throughput: all frames / wall time from the first step to the last bank's last step.
@@ -127,8 +127,8 @@ def run_banks(n_banks, n_seq, frames, max_fts, distinct=8, spec=None, device=0, 
         cam = synth.camera(spec)
         pick = [seqs[q % len(seqs)] for q in range(n_seq)]
         m = vo.MultiVisualOdometry(cam, n_seq, max_fts, device=device, lib=vo.load_from(lib_path) if lib_path else None)
-        if no_numa_pin or device_select:
-            m.set_options(no_numa_pin=no_numa_pin, device_select=device_select)   # device_select: hso_vo_options.device_select
+        if no_numa_pin or device_select or ba_fused:
+            m.set_options(no_numa_pin=no_numa_pin, device_select=device_select, ba_fused=ba_fused)   # hso_vo_options.device_select / .ba_fused
         m.set_first_frames([q["images"][0] for q in pick], [q["depth0"] for q in pick])
         threads_per_bank[b] = int(m.lib.hso_vo_multi_threads(m.h))
         if host_images:
@@ -189,7 +189,7 @@ def run_banks(n_banks, n_seq, frames, max_fts, distinct=8, spec=None, device=0, 
     c1 = _cgroup_cpu()
     ru1 = resource.getrusage(resource.RUSAGE_SELF)
     out = dict(banks=n_banks, sequences_per_bank=n_seq, sequences=n_banks * n_seq, frames=frames - 1, max_fts=max_fts, images="page-locked host" if host_images else "device",
-               device_select=bool(device_select), distinct=len(seqs), frames_per_s=n_banks * n_seq * (frames - 1) / wall, wall_s=wall,
+               device_select=bool(device_select), ba_fused=bool(ba_fused), distinct=len(seqs), frames_per_s=n_banks * n_seq * (frames - 1) / wall, wall_s=wall,
                ms_per_step_mean_per_bank=[r["ms_per_step_mean"] for r in res], ms_per_step_median_per_bank=[r["ms_per_step_median"] for r in res],
                keyframes_per_sequence=float(np.mean([r["keyframes"] for r in res])),
                failures=sum(r["failures"] for r in res), trans_err_max=max(r["trans_err_max"] for r in res))
@@ -227,7 +227,7 @@ if __name__ == "__main__":
     if sys.argv[1] == "banks":
         a = [int(x) for x in sys.argv[2:]]
         print(json.dumps(run_banks(a[0], a[1], a[2], a[3], a[4] if len(a) > 4 else 8, no_numa_pin=(len(a) > 5 and a[5] != 0),
-                                   device_select=(len(a) > 6 and a[6] != 0))))   # sixth / seventh number != 0: hso_vo_options.no_numa_pin / .device_select
+                                   device_select=(len(a) > 6 and a[6] != 0), ba_fused=(len(a) > 7 and a[7] != 0))))   # sixth / seventh / eighth number != 0: hso_vo_options.no_numa_pin / .device_select / .ba_fused
     else:
         a = [int(x) for x in sys.argv[1:]]
         print(json.dumps(run(a[0], a[1], a[2], a[3] if len(a) > 3 else 8, on_device=(a[4] != 0 if len(a) > 4 else True))))

@@ -277,7 +277,10 @@ class GpuOptions(C.Structure):
     # hso_gpu_options (include/hso_gpu.h): per-context kernel-shape / wait choices; zero = default
     _fields_ = [("size", C.c_int32), ("wait_mode", C.c_int32), ("track_no_coop", C.c_int32), ("track_coop_scatter", C.c_int32),
                 ("track_coop_feats_per_wg", C.c_int32), ("track_coop_workgroups", C.c_int32), ("reserved", C.c_int32 * 2),
-                ("eager_gradients", C.c_int32)]
+                ("eager_gradients", C.c_int32), ("ba_fused", C.c_int32)]
+
+
+BA_FUSED_ROUNDS = 16   # hso_amd/csrc/hso_ba.hip: Levenberg rounds one k_ba_rounds launch carries (hso_gpu_options.ba_fused)
 
 
 class HsoGpuError(RuntimeError):
@@ -432,7 +435,7 @@ EXPORTED_SYMBOLS = [
 # ... and every symbol include/hso_gpu_debug.h declares (parity / trace read-backs, developer probes: not part of the boundary)
 DEBUG_SYMBOLS = ["hso_gpu_debug_census", "hso_gpu_klt_debug_level", "hso_gpu_seq_debug_list", "hso_gpu_seq_debug_ref_table", "hso_gpu_debug_fetch",
                  "hso_gpu_seqmap_debug_dump", "hso_gpu_seq_ba_debug_window", "hso_gpu_debug_sobel_taps", "hso_gpu_debug_frame_stats",
-                 "hso_gpu_debug_wave_primitives", "hso_gpu_rectify_map_read"]
+                 "hso_gpu_debug_wave_primitives", "hso_gpu_rectify_map_read", "hso_gpu_ba_debug_launches"]
 
 
 def select_octree(keys, width, height, n_features):
@@ -519,11 +522,12 @@ class Context:
         self._check(self.lib.hso_gpu_synchronize(self.h), "synchronize")
 
     def configure(self, wait_mode=0, track_no_coop=False, track_coop_scatter=False, track_coop_feats_per_wg=0, track_coop_workgroups=0,
-                  eager_gradients=False):
+                  eager_gradients=False, ba_fused=False):
         """hso_gpu_configure: the context's kernel-shape / wait choices (every call sets all of them; no arguments = the defaults)"""
         o = GpuOptions(C.sizeof(GpuOptions), int(wait_mode), int(bool(track_no_coop)), int(bool(track_coop_scatter)), int(track_coop_feats_per_wg),
                        int(track_coop_workgroups))
         o.eager_gradients = int(bool(eager_gradients))
+        o.ba_fused = int(ba_fused)   # (not through bool(): the library refuses anything but 0 / 1)
         self._check(self.lib.hso_gpu_configure(self.h, C.byref(o)), "configure")
 
     def device_cpulist(self):
@@ -870,6 +874,13 @@ class Context:
             j.n_poses = len(poses); j.n_points = len(idist); j.n_edges = len(edges)
         self._check(self.lib.hso_gpu_ba_huber_deltas_multi(self.h, jobs, len(windows), error_multiplier2), "ba_huber_deltas_multi")
         return [(jobs[i].huber_corner, jobs[i].huber_edge) for i in range(len(windows))]
+
+    def ba_debug_launches(self):
+        """hso_gpu_ba_debug_launches: (kernels the context's Levenberg loops have enqueued so far, the k_ba_rounds launches among them)"""
+        out = (C.c_int64 * 2)()
+        self.lib.hso_gpu_ba_debug_launches.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        self._check(self.lib.hso_gpu_ba_debug_launches(self.h, out), "ba_debug_launches")
+        return int(out[0]), int(out[1])
 
     def ba_optimize(self, poses, fixed, idist, edges, huber_corner, huber_edge, n_iter):
         """The LM optimisation of LocalBundleAdjustment.  Returns (poses, idist, edge_chi2, BaResult)."""

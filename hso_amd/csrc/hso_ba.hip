@@ -28,7 +28,6 @@
 #include <algorithm>
 #include <cmath>
 #include <functional>
-#include <mutex>
 #include <vector>
 
 using namespace hso_dev;
@@ -180,13 +179,16 @@ HSO_HD void se3quat_exp_times(const double* upd, hso_se3& pose)
 }
 
 
+// The kernels' bodies are device functions of (window, virtual block): `vb` stands where blockIdx.x stood and `nvb` where gridDim.x
+// did, the LDS scratch comes from the caller.  A body reads them only to pick the slice of the window it owns, so a window's result
+// depends on that decomposition alone and not on how many workgroups really run: the __global__ kernels below pass blockIdx.x /
+// gridDim.x (one workgroup per virtual block), k_ba_rounds walks a window's virtual blocks with ONE workgroup — same 256-thread
+// shape, same order of sums, same bits.
 template <bool LIN>   // LIN = false: errors, chi2 and rho only (an LM trial's computeActiveErrors)
-__global__ __launch_bounds__(BA_THREADS) void k_ba_edges(const BaProb* probs, const BaLmDev* lm, int mask)
+__device__ __forceinline__ void ba_edges_body(const BaProb& P, int vb)
 {
-  const BaProb* PP = ba_window(probs, lm, mask);
-  if (!PP) return;
-  const BaArgs a = PP->a;
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  const BaArgs a = P.a;
+  const int k = vb * BA_THREADS + threadIdx.x;
   if (k >= a.n_edges) return;
   const hso_ba_edge e = a.edges[k];
   // SE3(Quaterniond, Vector3d) normalises (so3.cpp:43-47); Tth = Ttw * Thw^-1
@@ -280,6 +282,13 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_edges(const BaProb* probs, co
   a.edge_chi2[k] = chi2;
   a.edge_rho[k] = rho0;
 }
+template <bool LIN>
+__global__ __launch_bounds__(BA_THREADS) void k_ba_edges(const BaProb* probs, const BaLmDev* lm, int mask)
+{
+  const BaProb* PP = ba_window(probs, lm, mask);
+  if (!PP) return;
+  ba_edges_body<LIN>(*PP, blockIdx.x);
+}
 
 struct EdgeLin {
   double err[2], Jp[2], Jh[12], Jt[12], omega, om, rho1;
@@ -309,15 +318,12 @@ HSO_DEV double ba_omega_r(const BaArgs& a, int k, const EdgeLin& L, int d)
   return -(om * L.err[d]) * rho1;
 }
 
-__global__ __launch_bounds__(BA_THREADS) void k_ba_points(const BaProb* probs, const BaLmDev* lm, int mask)
+__device__ __forceinline__ void ba_points_body(const BaProb& P, int vb)
 {
-  const BaProb* PP = ba_window(probs, lm, mask);
-  if (!PP) return;
-  const BaProb& P = *PP;
   const BaArgs a = P.a;
   const int* pt_off = P.off; const int* pt_edges = P.list;
   double* Hpp = P.Hpp; double* bp = P.bp; double* Hpc = P.Hpc;
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  const int p = vb * BA_THREADS + threadIdx.x;
   if (p >= a.n_points) return;
   double hpp = 0, b = 0;
   for (int q = pt_off[p]; q < pt_off[p + 1]; q++) {
@@ -354,22 +360,24 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_points(const BaProb* probs, c
   }
   Hpp[p] = hpp; bp[p] = b;
 }
+__global__ __launch_bounds__(BA_THREADS) void k_ba_points(const BaProb* probs, const BaLmDev* lm, int mask)
+{
+  const BaProb* PP = ba_window(probs, lm, mask);
+  if (!PP) return;
+  ba_points_body(*PP, blockIdx.x);
+}
 
 // pr_off / pr_edges: CSR of the edges that touch each block's pose pair (host-built, edge order
 // kept): diagonal block i lists every edge with host == i or target == i, block (i, j) every edge
 // whose two frames are {i, j} — a block reads only its own edges instead of scanning all of them.
-__global__ __launch_bounds__(BA_THREADS) void k_ba_poses(const BaProb* probs, const BaLmDev* lm, int mask)
+__device__ __forceinline__ void ba_poses_body(const BaProb& P, int vb, double (*s_part)[44])   // s_part: [BA_WAVES][44]
 {
-  __shared__ double s_part[BA_WAVES][44];
-  const BaProb* PP = ba_window(probs, lm, mask);
-  if (!PP) return;
-  const BaProb& P = *PP;
   const BaArgs a = P.a;
   const int* pr_off = P.poff; const int* pr_edges = P.plist;
   double* Hcc = P.Hcc; double* bc = P.bc; double* chi2_sum = P.sum;
   // block -> (i, j), i <= j; one extra block sums the chi2 values
   const int np = a.n_poses;
-  int b = blockIdx.x, i = 0;
+  int b = vb, i = 0;
   const int n_pairs = np * (np + 1) / 2;
   if (b > n_pairs) return;   // the grid is sized for the largest window of the launch
   const bool chi_block = (b == n_pairs);
@@ -454,15 +462,19 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_poses(const BaProb* probs, co
     else if (i == j && threadIdx.x < 42) bc[i * 6 + threadIdx.x - 36] = t;
   }
 }
+__global__ __launch_bounds__(BA_THREADS) void k_ba_poses(const BaProb* probs, const BaLmDev* lm, int mask)
+{
+  __shared__ double s_part[BA_WAVES][44];
+  const BaProb* PP = ba_window(probs, lm, mask);
+  if (!PP) return;
+  ba_poses_body(*PP, blockIdx.x, s_part);
+}
 
 
 // the blocks a linearisation accumulates into, zeroed for every window of the launch at once (was: one memset per window)
-__global__ __launch_bounds__(BA_THREADS) void k_ba_begin(const BaProb* probs, const BaLmDev* lm)
+__device__ __forceinline__ void ba_begin_body(const BaProb& P, int want, int vb, int nvb)
 {
-  const int want = lm ? lm[blockIdx.y].want : BA_W_LINEARIZE;
-  if (!(want & (BA_W_RESTORE | BA_W_LINEARIZE))) return;
-  const BaProb& P = probs[blockIdx.y];
-  const size_t first = (size_t)blockIdx.x * BA_THREADS + threadIdx.x, step = (size_t)gridDim.x * BA_THREADS;
+  const size_t first = (size_t)vb * BA_THREADS + threadIdx.x, step = (size_t)nvb * BA_THREADS;
   if (want & BA_W_RESTORE) {                                        // g2o's pop(): the state before the rejected step
     for (size_t p = first; p < (size_t)P.a.n_points; p += step) P.idist_rw[p] = P.idist_bak[p];
     for (size_t i = first; i < (size_t)P.a.n_poses; i += step) P.poses_rw[i] = P.poses_bak[i];
@@ -473,16 +485,18 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_begin(const BaProb* probs, co
     for (size_t i = first; i < n; i += step) z[i] = make_uint4(0, 0, 0, 0);
   }
 }
+__global__ __launch_bounds__(BA_THREADS) void k_ba_begin(const BaProb* probs, const BaLmDev* lm)
+{
+  const int want = lm ? lm[blockIdx.y].want : BA_W_LINEARIZE;
+  if (!(want & (BA_W_RESTORE | BA_W_LINEARIZE))) return;
+  ba_begin_body(probs[blockIdx.y], want, blockIdx.x, gridDim.x);
+}
 
 // computeLambdaInit (thirdparty/g2o/g2o/core/optimization_algorithm_levenberg.cpp:191-201): the largest |diagonal entry| of the
 // Hessian blocks of every free vertex — points: Hpp, free poses: the diagonal of their Hcc block — into sum[5].  A maximum does
 // not depend on the order it is taken in; the host used to read Hpp and the whole Hcc table of every window for this one number.
-__global__ __launch_bounds__(BA_THREADS) void k_ba_maxdiag(const BaProb* probs, const BaLmDev* lm, int mask)
+__device__ __forceinline__ void ba_maxdiag_body(const BaProb& P, double* s_part)   // s_part: [BA_WAVES]
 {
-  __shared__ double s_part[BA_WAVES];
-  const BaProb* PP = ba_window(probs, lm, mask);
-  if (!PP) return;
-  const BaProb& P = *PP;
   const int np = P.a.n_poses;
   double m = 0;
   for (int p = threadIdx.x; p < P.a.n_points; p += BA_THREADS) m = fmax(m, fabs(P.Hpp[p]));
@@ -495,6 +509,13 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_maxdiag(const BaProb* probs, 
   if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = m;
   __syncthreads();
   if (threadIdx.x == 0) { double t = 0; for (int w = 0; w < BA_WAVES; w++) t = fmax(t, s_part[w]); P.sum[5] = t; }
+}
+__global__ __launch_bounds__(BA_THREADS) void k_ba_maxdiag(const BaProb* probs, const BaLmDev* lm, int mask)
+{
+  __shared__ double s_part[BA_WAVES];
+  const BaProb* PP = ba_window(probs, lm, mask);
+  if (!PP) return;
+  ba_maxdiag_body(*PP, s_part);
 }
 
 // The accept / reject decision of OptimizationAlgorithmLevenberg::solve (optimization_algorithm_levenberg.cpp:61-164) and the
@@ -580,17 +601,9 @@ __device__ void ba_decide(const double* sum, BaLmDev& L, double* lam_next)
 
 // sum of chi2 and of the robustified rho(chi2) over all edges (activeChi2 / activeRobustChi2,
 // thirdparty/g2o/g2o/core/sparse_optimizer.cpp:100-113): one workgroup, fixed tree => deterministic
-__global__ __launch_bounds__(BA_THREADS) void k_ba_chi2(const BaProb* probs, BaLmDev* lm, int mask, int with_scale, double* lam_next)
+// (L: the window's state record, null outside the loop; lam_next: the window's damping slot)
+__device__ __forceinline__ void ba_chi2_body(const BaProb& P, BaLmDev* L, int with_scale, double* lam_next, double (*s_part)[2])   // s_part: [BA_WAVES][2]
 {
-  __shared__ double s_part[BA_WAVES][2];
-  // a window whose last step was rejected spends one more round restoring (k_ba_begin): that round ends here
-  if (lm && mask == BA_W_TRIAL && lm[blockIdx.y].st == BA_ST_FINAL_WAIT) {
-    if (threadIdx.x == 0) { lm[blockIdx.y].st = BA_ST_DONE; lm[blockIdx.y].want = 0; }
-    return;
-  }
-  const BaProb* PP = ba_window(probs, lm, mask);
-  if (!PP) return;
-  const BaProb& P = *PP;
   const BaArgs a = P.a;
   double* chi2_sum = P.sum;
   double c = 0, r = 0;
@@ -610,10 +623,22 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_chi2(const BaProb* probs, BaL
   }
   // the end of an LM trial: the points' part of computeScale from k_ba_backsub's workgroups, in index order
   if (with_scale && threadIdx.x == 2) { double t = 0; for (int g = 0; g < BA_BACKSUB_BLOCKS; g++) t += P.part[g]; chi2_sum[2] = t; }
-  if (!lm) return;
+  if (!L) return;
   __threadfence_block();
   __syncthreads();
-  if (threadIdx.x == 0) ba_decide(chi2_sum, lm[blockIdx.y], lam_next + blockIdx.y);
+  if (threadIdx.x == 0) ba_decide(chi2_sum, *L, lam_next);
+}
+__global__ __launch_bounds__(BA_THREADS) void k_ba_chi2(const BaProb* probs, BaLmDev* lm, int mask, int with_scale, double* lam_next)
+{
+  __shared__ double s_part[BA_WAVES][2];
+  // a window whose last step was rejected spends one more round restoring (k_ba_begin): that round ends here
+  if (lm && mask == BA_W_TRIAL && lm[blockIdx.y].st == BA_ST_FINAL_WAIT) {
+    if (threadIdx.x == 0) { lm[blockIdx.y].st = BA_ST_DONE; lm[blockIdx.y].want = 0; }
+    return;
+  }
+  const BaProb* PP = ba_window(probs, lm, mask);
+  if (!PP) return;
+  ba_chi2_body(*PP, lm ? lm + blockIdx.y : nullptr, with_scale, lam_next + blockIdx.y, s_part);
 }
 
 // The reduced system of one LM trial on the device: S = Hcc_free + lambda I - sum_p Hpc_p^T (Hpp_p + lambda)^-1 Hpc_p and
@@ -621,14 +646,10 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_chi2(const BaProb* probs, BaL
 // pose-pair block (i <= j) of the window: threads stride over the points (rows of Hpc of unconnected poses are zero), then
 // the fixed tree of k_ba_poses; the block writes its 6x6 piece to both triangles of S.  Only M * M + M doubles go back to the
 // host for the dense factorisation — not the n_points x n_poses x 6 block table.
-__global__ __launch_bounds__(BA_THREADS) void k_ba_schur(const BaProb* probs, const BaLmDev* lm, int mask)
+__device__ __forceinline__ void ba_schur_body(const BaProb& P, int vb, double (*s_part)[44])   // s_part: [BA_WAVES][44]
 {
-  __shared__ double s_part[BA_WAVES][44];
-  const BaProb* PP = ba_window(probs, lm, mask);
-  if (!PP) return;
-  const BaProb& P = *PP;
   const int np = P.a.n_poses, n_pairs = np * (np + 1) / 2, M = P.M;
-  int b = blockIdx.x, i = 0;
+  int b = vb, i = 0;
   if (b > n_pairs) return;
   const double lambda = ba_lambda(P);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -688,6 +709,13 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_schur(const BaProb* probs, co
     }
   }
 }
+__global__ __launch_bounds__(BA_THREADS) void k_ba_schur(const BaProb* probs, const BaLmDev* lm, int mask)
+{
+  __shared__ double s_part[BA_WAVES][44];
+  const BaProb* PP = ba_window(probs, lm, mask);
+  if (!PP) return;
+  ba_schur_body(*PP, blockIdx.x, s_part);
+}
 
 // The dense LDL^T of the reduced system (no pivoting, like the reference's SimplicialLDLT), the triangular solves, the pose
 // part of computeScale and the pose update SE3Quat::exp(dx) * pose — one workgroup per window, the matrix in LDS.
@@ -696,14 +724,10 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_schur(const BaProb* probs, co
 // over the threads; the substitutions are column sweeps (x_k final, then x_i -= L_ik x_k for all i at once).  A vanishing or
 // non-finite pivot, or a point diagonal that cannot be inverted (flag from k_ba_schur), means "no step": g2o's solver reports
 // failure and the trial is rejected.
-__global__ __launch_bounds__(BA_THREADS) void k_ba_solve(const BaProb* probs, const BaLmDev* lm, int mask)
+// LDS: s_S [M * M], s_x [96], s_col [96], s_sc [16] (one entry per FREE pose: M <= 96 unknowns = 16 poses), s_ok_ [1]
+__device__ __forceinline__ void ba_solve_body(const BaProb& P, double* s_S, double* s_x, double* s_col, double* s_sc, int* s_ok_)
 {
-  extern __shared__ double s_S[];
-  __shared__ double s_x[96], s_col[96], s_sc[16];   // s_sc: one entry per FREE pose (M <= 96 unknowns = 16 poses)
-  __shared__ int s_ok;
-  const BaProb* PP = ba_window(probs, lm, mask);
-  if (!PP) return;
-  const BaProb& P = *PP;
+  int& s_ok = *s_ok_;
   const int M = P.M, np = P.a.n_poses, tid = threadIdx.x;
   const double lambda = ba_lambda(P);
   for (int q = tid; q < M * M; q += BA_THREADS) s_S[q] = P.S[q];
@@ -771,6 +795,15 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_solve(const BaProb* probs, co
     P.sum[4] = ok ? 1.0 : 0.0;
   }
 }
+__global__ __launch_bounds__(BA_THREADS) void k_ba_solve(const BaProb* probs, const BaLmDev* lm, int mask)
+{
+  extern __shared__ double s_S[];
+  __shared__ double s_x[96], s_col[96], s_sc[16];
+  __shared__ int s_ok;
+  const BaProb* PP = ba_window(probs, lm, mask);
+  if (!PP) return;
+  ba_solve_body(*PP, s_S, s_x, s_col, s_sc, &s_ok);
+}
 
 // Back-substitution of the points, their update and the point part of computeScale: x_p = (bp_p - Hpc_p . xc) / (Hpp_p +
 // lambda) with the poses in index order (products with the zero rows of unconnected poses change nothing, so the value
@@ -778,18 +811,14 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_solve(const BaProb* probs, co
 // (one workgroup streamed a window's 2-3 MB of Hpc rows at the latency of 256 threads: 53 us per launch, 8.5 launches per window):
 // workgroup g takes the points g * 256 + t, g * 256 + t + 16 * 256, ... and leaves its part of the scale in part[g]; k_ba_chi2,
 // which ends every trial, adds the parts in index order — a fixed tree, whatever else runs beside the window.
-__global__ __launch_bounds__(BA_THREADS) void k_ba_backsub(const BaProb* probs, const BaLmDev* lm, int mask)
+__device__ __forceinline__ void ba_backsub_body(const BaProb& P, int vb, double* s_part)   // s_part: [BA_WAVES]; vb < BA_BACKSUB_BLOCKS
 {
-  __shared__ double s_part[BA_WAVES];
-  const BaProb* PP = ba_window(probs, lm, mask);
-  if (!PP) return;
-  const BaProb& P = *PP;
   const int np = P.a.n_poses;
   const double lambda = ba_lambda(P);
   const double* xc = P.trial + 1;
   const bool no_step = P.trial[1 + 6 * np] != 0.0;   // the reduced system could not be solved: x = 0 (the trial is rejected)
   double sc = 0;
-  for (int p = blockIdx.x * BA_THREADS + threadIdx.x; p < P.a.n_points; p += BA_BACKSUB_BLOCKS * BA_THREADS) {
+  for (int p = vb * BA_THREADS + threadIdx.x; p < P.a.n_points; p += BA_BACKSUB_BLOCKS * BA_THREADS) {
     const double dpp = P.Hpp[p] + lambda;
     const double inv = 1.0 / dpp;
     double s = P.bp[p];
@@ -809,7 +838,76 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_backsub(const BaProb* probs, 
   sc = wave_butterfly_sum(sc);
   if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = sc;
   __syncthreads();
-  if (threadIdx.x == 0) { double t = 0; for (int w = 0; w < BA_WAVES; w++) t += s_part[w]; P.part[blockIdx.x] = t; }
+  if (threadIdx.x == 0) { double t = 0; for (int w = 0; w < BA_WAVES; w++) t += s_part[w]; P.part[vb] = t; }
+}
+__global__ __launch_bounds__(BA_THREADS) void k_ba_backsub(const BaProb* probs, const BaLmDev* lm, int mask)
+{
+  __shared__ double s_part[BA_WAVES];
+  const BaProb* PP = ba_window(probs, lm, mask);
+  if (!PP) return;
+  ba_backsub_body(*PP, blockIdx.x, s_part);
+}
+
+// hso_gpu_options.ba_fused: a window's Levenberg rounds in ONE launch.  One workgroup per window (blockIdx.x = window) runs, per round,
+// the phases ba_run enqueues as kernels — the errors-only round (the call's first round only), restore / begin, edges<true>, points,
+// poses, maxdiag, then schur, solve, backsub, edges<false>, chi2 + ba_decide — each phase by walking its virtual blocks one after the
+// other through the bodies above, a workgroup barrier behind every virtual block that used the LDS scratch and between phases.  A
+// phase asks the state record what the window wants exactly where its kernel would, so the window goes through the states it goes
+// through on the unfused path and every table holds the same bits.
+//   It ends by construction: the round loop counts to the launch argument, nothing in it waits for another workgroup or for a flag.
+// A window needs at most 1 + 5 n_iter + 1 rounds (ba_decide: five trials per iteration, the errors-only round, the last restore);
+// one that is not done after max_rounds stays in its state record, and ba_run's read-back of the states continues it with another
+// launch.  What a phase reads from global memory an earlier phase of the same workgroup wrote: __syncthreads() orders that at
+// workgroup scope, and no table is read through a pointer that promises the compiler anything (no __restrict__, no __ldg).
+__global__ __launch_bounds__(BA_THREADS) void k_ba_rounds(const BaProb* probs, BaLmDev* lm, double* lam_next, int max_rounds, int errors_round)
+{
+  extern __shared__ double s_S[];                        // the solve's matrix
+  __shared__ double s_part[BA_WAVES * 44];               // every other phase's partial sums, one virtual block at a time
+  __shared__ double s_x[96], s_col[96], s_sc[16];
+  __shared__ int s_ok;
+  const BaProb& P = probs[blockIdx.x];
+  BaLmDev& L = lm[blockIdx.x];
+  double* lam = lam_next + blockIdx.x;
+  double (*s44)[44] = reinterpret_cast<double (*)[44]>(s_part);
+  const int nb_edges = (P.a.n_edges + BA_THREADS - 1) / BA_THREADS, nb_points = (P.a.n_points + BA_THREADS - 1) / BA_THREADS;
+  const int nb_pairs = P.a.n_poses * (P.a.n_poses + 1) / 2 + 1;   // + the extra block (chi2 sums / the "solvable" flag)
+  for (int r = 0; r < max_rounds; r++) {
+    if (L.st == BA_ST_DONE) break;                       // uniform: the record was last written in front of a barrier
+    if (errors_round && r == 0) {
+      if (L.want & BA_W_ERRORS) {
+        for (int vb = 0; vb < nb_edges; vb++) ba_edges_body<false>(P, vb);
+        __syncthreads();
+        ba_chi2_body(P, &L, 0, lam, reinterpret_cast<double (*)[2]>(s_part));
+      }
+      __syncthreads();
+    }
+    const int want = L.want;
+    if (want & (BA_W_RESTORE | BA_W_LINEARIZE)) ba_begin_body(P, want, 0, 1);
+    __syncthreads();
+    if (L.want & BA_W_LINEARIZE) {
+      for (int vb = 0; vb < nb_edges; vb++) ba_edges_body<true>(P, vb);
+      __syncthreads();
+      for (int vb = 0; vb < nb_points; vb++) ba_points_body(P, vb);
+      __syncthreads();
+      for (int vb = 0; vb < nb_pairs; vb++) { ba_poses_body(P, vb, s44); __syncthreads(); }
+      ba_maxdiag_body(P, s_part);
+      __syncthreads();
+    }
+    if (L.want & BA_W_TRIAL) {
+      for (int vb = 0; vb < nb_pairs; vb++) { ba_schur_body(P, vb, s44); __syncthreads(); }
+      ba_solve_body(P, s_S, s_x, s_col, s_sc, &s_ok);
+      __syncthreads();
+      for (int vb = 0; vb < BA_BACKSUB_BLOCKS; vb++) { ba_backsub_body(P, vb, s_part); __syncthreads(); }
+      for (int vb = 0; vb < nb_edges; vb++) ba_edges_body<false>(P, vb);
+      __syncthreads();
+    }
+    // the end of the round, as in k_ba_chi2: a window that only restored is done, one that made a trial decides
+    const int st_end = L.st, want_end = L.want;          // every thread has read the record before thread 0 writes it
+    __syncthreads();
+    if (st_end == BA_ST_FINAL_WAIT) { if (threadIdx.x == 0) { L.st = BA_ST_DONE; L.want = 0; } }
+    else if (want_end & BA_W_TRIAL) ba_chi2_body(P, &L, 1, lam, reinterpret_cast<double (*)[2]>(s_part));
+    __syncthreads();
+  }
 }
 
 // g2o's pop() for the points: the state before the rejected step
@@ -1347,6 +1445,7 @@ namespace {
 // told which read-backs to make; value-passing windows hand their state back to the caller's arrays.
 #define BA_ROUNDS_FIRST 10
 #define BA_ROUNDS_MORE 4
+#define BA_FUSED_ROUNDS 16   // hso_gpu_options.ba_fused: rounds per k_ba_rounds launch (the engine's windows take 8-14 at 2000 features: profiles/r9_ba_fused.md)
 struct BaLmHost {   // what the caller gives and gets per window
   hso_se3* poses_f_w; double* idist; double* edge_chi2_out; hso_ba_result* result; int n_iter;
 };
@@ -1368,25 +1467,35 @@ static int ba_run(hso_gpu_ctx* ctx, BaBatch& Q, const std::vector<BaLmHost>& lm,
     Q.h_lambda[q] = -1.0;
   }
   HSO_HIP_CHECK(ctx, hipMemcpyAsync(Q.d_lm, Q.h_lm, (size_t)(reinterpret_cast<char*>(Q.h_lambda + n) - reinterpret_cast<char*>(Q.h_lm)), hipMemcpyHostToDevice, ctx->stream));
-  // 96 x 96 doubles = 72 KiB of dynamic LDS: above the 64 KiB a launch gets without asking (once per process; several engines call this
-  // function from their own threads)
-  static std::once_flag solve_attr;
-  hipError_t attr_rc = hipSuccess;
-  std::call_once(solve_attr, [&] { attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ba_solve), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 96 * (int)sizeof(double)); });
-  HSO_HIP_CHECK(ctx, attr_rc);
+  // 96 x 96 doubles = 72 KiB of dynamic LDS: above the 64 KiB a launch gets without asking.  The attribute belongs to the device the
+  // call is made on, so it is set once per context (ba_batch_begin made the context's device current) and a failure reaches every caller
+  if (!ctx->ba_lds_attr) {
+    HSO_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_ba_solve), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 96 * (int)sizeof(double)));
+    HSO_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_ba_rounds), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 96 * (int)sizeof(double)));
+    ctx->ba_lds_attr = true;
+  }
+  const bool fused = ctx->opt.ba_fused != 0;
   const int max_m = ba_max(Q, &BaWin::M), max_pairs = ba_max(Q, &BaWin::n_pairs);
   std::vector<BaLmDev> state((size_t)n);
   std::vector<float> hub(2 * (size_t)n);
   bool first = true;
   for (int rounds = BA_ROUNDS_FIRST;; rounds = BA_ROUNDS_MORE) {
-    for (int r = 0; r < rounds; r++) {
+    if (fused) {
+      hipLaunchKernelGGL(k_ba_rounds, dim3(n), dim3(BA_THREADS), sizeof(double) * (size_t)std::max(max_m * max_m, 1), ctx->stream, Q.d_probs, Q.d_lm, Q.d_lambda,
+                         (int)BA_FUSED_ROUNDS, (first && any_errors_round) ? 1 : 0);
+      HSO_HIP_CHECK(ctx, hipGetLastError());
+      ctx->ba_launches[0]++; ctx->ba_launches[1]++;
+      first = false;
+    }
+    for (int r = 0; r < rounds && !fused; r++) {
       // (the errors-only round of a window that runs zero iterations: only the call's first round can hold one)
-      if (first && any_errors_round) { if (int rc = ba_launch_errors(Q, Q.d_lm, BA_W_ERRORS)) return rc; }
+      if (first && any_errors_round) { if (int rc = ba_launch_errors(Q, Q.d_lm, BA_W_ERRORS)) return rc; ctx->ba_launches[0] += 2; }
       if (int rc = ba_launch_linearize(Q, Q.d_lm)) return rc;
       hipLaunchKernelGGL(k_ba_schur, dim3(max_pairs + 1, n), dim3(BA_THREADS), 0, ctx->stream, Q.d_probs, Q.d_lm, (int)BA_W_TRIAL);
       hipLaunchKernelGGL(k_ba_solve, dim3(1, n), dim3(BA_THREADS), sizeof(double) * (size_t)std::max(max_m * max_m, 1), ctx->stream, Q.d_probs, Q.d_lm, (int)BA_W_TRIAL);
       hipLaunchKernelGGL(k_ba_backsub, dim3(BA_BACKSUB_BLOCKS, n), dim3(BA_THREADS), 0, ctx->stream, Q.d_probs, Q.d_lm, (int)BA_W_TRIAL);
       if (int rc = ba_launch_errors(Q, Q.d_lm, BA_W_TRIAL)) return rc;   // ... and the round's decision (ba_decide)
+      ctx->ba_launches[0] += 10;
       first = false;
     }
     // what comes back: the state records (is every window done?), once the Huber deltas, and the finished windows' results
@@ -1449,6 +1558,14 @@ static int ba_optimize_multi_impl(hso_gpu_ctx* ctx, const hso_ba_problem* proble
     lm[(size_t)q] = {P.poses_f_w, P.idist, P.edge_chi2_out, P.result, P.n_iter};
   }
   return ba_run(ctx, Q, lm, obs_uv ? huber_out : nullptr, nullptr);
+}
+
+extern "C" int hso_gpu_ba_debug_launches(hso_gpu_ctx* ctx, int64_t out[2])
+{
+  if (!ctx) return HSO_E_INVALID;
+  if (!out) return hso_fail(ctx, HSO_E_INVALID, "ba_debug_launches: bad argument");
+  out[0] = ctx->ba_launches[0]; out[1] = ctx->ba_launches[1];
+  return HSO_OK;
 }
 
 extern "C" int hso_gpu_ba_optimize_multi(hso_gpu_ctx* ctx, const hso_ba_problem* problems, int n_problems)

@@ -72,6 +72,8 @@ struct hso_gpu_ctx {
   // hso_gpu_seq_local_ba: the window assembly's per-job tables (they outlive the batch's own area: the write-back reads them), and what
   // hso_gpu_seq_ba_debug_window serves
   char* d_rba = nullptr; size_t rba_cap = 0; struct RbaLast* rba_last = nullptr;
+  bool ba_lds_attr = false;           // the dynamic-LDS attribute of k_ba_solve / k_ba_rounds is set on this context's device
+  int64_t ba_launches[2] = {0, 0};    // hso_gpu_ba_debug_launches: BA round kernels enqueued, k_ba_rounds launches among them
   // between the three kernels of a seed observation (hso_seed.hip): [SeedPre | SeedMid] per seed, grow-only
   char* d_seed_scratch; size_t seed_scratch_cap;
   // The depth filter's own stream (the reference runs it on its own thread, src/depth_filter.cpp:130-162): the previous-frame pass

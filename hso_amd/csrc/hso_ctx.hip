@@ -620,7 +620,7 @@ int hso_gpu_configure(hso_gpu_ctx* ctx, const hso_gpu_options* o)
   hso_gpu_options n{};
   memcpy(&n, o, (size_t)o->size);
   if (n.wait_mode < HSO_WAIT_DEFAULT || n.wait_mode > HSO_WAIT_BLOCK || n.track_coop_feats_per_wg < 0 || n.track_coop_workgroups < 0 ||
-      n.eager_gradients < 0 || n.eager_gradients > 1)
+      n.eager_gradients < 0 || n.eager_gradients > 1 || n.ba_fused < 0 || n.ba_fused > 1)
     return hso_fail(ctx, HSO_E_INVALID, "configure: value out of range");
   ctx->opt = n;
   hso_apply_wait_mode(ctx);

@@ -236,7 +236,7 @@ bool Bank::resize_available()
   return hso_gpu_frame_upload_batch_resized && hso_gpu_frame_download_level;
 }
 
-void Bank::set_options(bool sync_previous, bool track_no_coop, bool no_numa_pin, bool device_select, bool rectify, bool resize)
+void Bank::set_options(bool sync_previous, bool track_no_coop, bool no_numa_pin, bool device_select, bool rectify, bool resize, bool ba_fused)
 {
   // before anything changes: the harness's `if(cam_->getUndistort())` (test/test_dataset.cpp:276) holds for a FOV camera built with
   // undistort = true and for an Equidistant camera, and for no other
@@ -258,7 +258,13 @@ void Bank::set_options(bool sync_previous, bool track_no_coop, bool no_numa_pin,
   device_select_ = device_select;
   hso_gpu_options o{};
   o.size = (int32_t)sizeof(o); o.track_no_coop = track_no_coop ? 1 : 0;
+  o.ba_fused = ba_fused ? 1 : 0;   // hso_vo_options.ba_fused: the kernel shape of hso_gpu_seq_local_ba's Levenberg loop
   check(hso_gpu_configure(ctx_, &o), "configure");
+}
+
+bool Bank::ba_launches(int64_t out[2]) const
+{
+  return hso_gpu_ba_debug_launches && hso_gpu_ba_debug_launches(ctx_, out) == HSO_OK;
 }
 
 void Bank::call_counts(int64_t* calls, int64_t* items, int cap) const

@@ -184,10 +184,11 @@ public:
   // rectify: throws Refused for a camera the reference does not rectify; the caller checks rectify_available() first
   // resize: images of any one size per call are accepted from now on; the caller checks resize_available() first
   void set_options(bool sync_previous, bool track_no_coop, bool no_numa_pin = false, bool device_select = false, bool rectify = false,
-                   bool resize = false);
+                   bool resize = false, bool ba_fused = false);
   static bool rectify_available();   // the device library linked in has hso_gpu_frame_upload_batch_rectified
   static bool resize_available();    // ... and hso_gpu_frame_upload_batch_resized
   void call_counts(int64_t* calls, int64_t* items, int cap) const;
+  bool ba_launches(int64_t out[2]) const;   // hso_gpu_ba_debug_launches of the bank's context; false: the device library has no such entry
   // algorithmic bytes (SURVEY.md section 8(d) units) of the steps so far: [frame build, tracker, matcher, pose optimiser, seeds]
   void alg_bytes(double* out, int cap) const { for (int i = 0; i < cap && i < 5; i++) out[i] = alg_bytes_[i]; }
   std::string err;

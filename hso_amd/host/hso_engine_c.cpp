@@ -75,7 +75,8 @@ static int set_opts(Bank* b, const hso_vo_options* o)
     if (!b->poisoned) b->err = "set_options: the device library has no batched resize entry (hso_gpu_frame_upload_batch_resized)";
     return HSO_E_UNSUPPORTED;
   }
-  return guarded(b, [&]() { b->set_options(o->sync_previous != 0, o->track_no_coop != 0, no_pin, device_select, rectify, resize); });
+  const bool ba_fused = o->size >= 32 && o->ba_fused != 0;
+  return guarded(b, [&]() { b->set_options(o->sync_previous != 0, o->track_no_coop != 0, no_pin, device_select, rectify, resize, ba_fused); });
 }
 int hso_vo_set_options(hso_vo* v, const hso_vo_options* o) { return v ? set_opts(v->bank, o) : HSO_E_INVALID; }
 int hso_vo_trace_state(hso_vo* v, int on) { return (v && v->bank->trace_state(0, on != 0)) ? HSO_OK : HSO_E_INVALID; }
@@ -150,6 +151,12 @@ int hso_vo_multi_get_trajectory(hso_vo_multi* m, int sequence, double* timestamp
   return m->bank->trajectory(sequence, timestamps, T_f_w, cap);
 }
 int hso_vo_get_trajectory(hso_vo* v, double* timestamps, hso_se3* T_f_w, int cap) { return v ? v->bank->trajectory(0, timestamps, T_f_w, cap) : HSO_E_INVALID; }
+int hso_vo_multi_ba_launches(hso_vo_multi* m, int64_t out[2])
+{
+  if (!m || !out) return HSO_E_INVALID;
+  return m->bank->ba_launches(out) ? HSO_OK : HSO_E_UNSUPPORTED;
+}
+
 int hso_vo_multi_call_counts(hso_vo_multi* m, int64_t* calls, int64_t* items, int cap)
 {
   if (!m) return HSO_E_INVALID;

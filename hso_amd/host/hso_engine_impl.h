@@ -19,6 +19,7 @@
 // rectification entries; there the addresses are null and hso_vo_options.rectify is answered with HSO_E_UNSUPPORTED.  In this header
 // because a weak reference is a property of the translation unit: every unit of the engine that names one of these sees them weak.
 extern "C" int hso_gpu_rectify_map_create(hso_gpu_ctx* ctx, const hso_camera* cam, int32_t* map_out) __attribute__((weak));
+extern "C" int hso_gpu_ba_debug_launches(hso_gpu_ctx* ctx, int64_t out[2]) __attribute__((weak));   // include/hso_gpu_debug.h (hso_vo_multi_ba_launches)
 extern "C" int hso_gpu_rectify_map_destroy(hso_gpu_ctx* ctx, int32_t map) __attribute__((weak));
 extern "C" int hso_gpu_frame_upload_batch_rectified(hso_gpu_ctx* ctx, const int64_t* frame_ids, const uint8_t* const* imgs, int n, int32_t map,
                                                     int img_is_device, hso_frame_stats* stats_out) __attribute__((weak));

@@ -25,9 +25,9 @@ class VoStatus(C.Structure):
 
 
 class VoOptions(C.Structure):
-    # hso_vo_options (include/hso_vo.h).  The header names the words after device_select `rectify` and `resize` and keeps one
-    # reserved word behind them; the binding keeps the three words as one array — its layout is pinned by
-    # tests/test_device_select_cpu.py — and names the first two through properties.
+    # hso_vo_options (include/hso_vo.h).  The header names the words after device_select `rectify`, `resize` and `ba_fused`; the
+    # binding keeps the three words as one array — its layout is pinned by tests/test_device_select_cpu.py — and names them
+    # through properties.
     _fields_ = [("size", C.c_int32), ("sync_previous", C.c_int32), ("track_no_coop", C.c_int32), ("no_numa_pin", C.c_int32), ("device_select", C.c_int32),
                 ("reserved", C.c_int32 * 3)]
 
@@ -46,6 +46,14 @@ class VoOptions(C.Structure):
     @resize.setter
     def resize(self, v):
         self.reserved[1] = int(v)
+
+    @property
+    def ba_fused(self):
+        return self.reserved[2]
+
+    @ba_fused.setter
+    def ba_fused(self, v):
+        self.reserved[2] = int(v)
 
 
 _lib = None
@@ -84,6 +92,7 @@ def _declare(lib):
     lib.hso_vo_multi_get_status.argtypes = [vp, i32, P(VoStatus)]
     lib.hso_vo_multi_get_keyframes.argtypes = [vp, i32, vp, vp, vp, i32]
     lib.hso_vo_multi_call_counts.argtypes = [vp, vp, vp, i32]
+    lib.hso_vo_multi_ba_launches.argtypes = [vp, vp]
     lib.hso_vo_host_share.argtypes = [i32]
     lib.hso_vo_multi_alg_bytes.argtypes = [vp, vp, i32]
     lib.hso_vo_multi_threads.argtypes = [vp]
@@ -113,7 +122,8 @@ EXPORTED_SYMBOLS = ["hso_vo_create", "hso_vo_destroy", "hso_vo_last_error", "hso
                     "hso_vo_add_image", "hso_vo_get_status", "hso_vo_get_keyframes", "hso_vo_start", "hso_vo_init_compute_matrix",
                     "hso_vo_multi_create", "hso_vo_multi_destroy", "hso_vo_multi_last_error", "hso_vo_multi_size",
                     "hso_vo_multi_set_first_frames", "hso_vo_multi_add_images", "hso_vo_multi_get_status", "hso_vo_multi_get_keyframes",
-                    "hso_vo_multi_call_counts", "hso_vo_host_share", "hso_vo_multi_alg_bytes", "hso_vo_multi_threads", "hso_vo_host_cpu_quota", "hso_vo_multi_start", "hso_vo_multi_trace", "hso_vo_multi_add_images_device", "hso_vo_multi_get_trajectory", "hso_vo_get_trajectory", "hso_vo_trace_state", "hso_vo_multi_trace_state", "hso_vo_set_options", "hso_vo_multi_set_options"]
+                    "hso_vo_multi_call_counts", "hso_vo_host_share", "hso_vo_multi_alg_bytes", "hso_vo_multi_threads", "hso_vo_host_cpu_quota", "hso_vo_multi_start", "hso_vo_multi_trace", "hso_vo_multi_add_images_device", "hso_vo_multi_get_trajectory", "hso_vo_get_trajectory", "hso_vo_trace_state", "hso_vo_multi_trace_state", "hso_vo_set_options", "hso_vo_multi_set_options",
+                    "hso_vo_multi_ba_launches"]
 
 CALL_KINDS = ["frame_upload", "frame_release", "track", "reproject_select_pose", "align", "pose", "seed_observe", "seed_activate", "ba", "other"]
 
@@ -158,13 +168,15 @@ class MultiVisualOdometry:
     def trace(self, k, path):
         self._check(self.lib.hso_vo_multi_trace(self.h, int(k), path.encode() if path else None), "trace")
 
-    def set_options(self, sync_previous=False, track_no_coop=False, no_numa_pin=False, device_select=False, rectify=False, resize=False):
+    def set_options(self, sync_previous=False, track_no_coop=False, no_numa_pin=False, device_select=False, rectify=False, resize=False, ba_fused=False):
         """rectify: the images handed over from now on are raw and the engine rectifies them on the device (hso_vo_options.rectify).
         resize: they may have any one size per call (sensor images); the engine resizes them to the camera's size on the device, in
-        front of the rectification (hso_vo_options.resize).  depth images stay camera-size."""
+        front of the rectification (hso_vo_options.resize).  depth images stay camera-size.
+        ba_fused: local BA runs a window's Levenberg rounds in one launch (hso_vo_options.ba_fused); same results."""
         o = VoOptions(C.sizeof(VoOptions), int(bool(sync_previous)), int(bool(track_no_coop)), int(bool(no_numa_pin)), int(bool(device_select)))
         o.rectify = int(bool(rectify))
         o.resize = int(bool(resize))
+        o.ba_fused = int(bool(ba_fused))
         self._check(self.lib.hso_vo_multi_set_options(self.h, C.byref(o)), "set_options")
 
     def start(self, which=None):
@@ -213,6 +225,12 @@ class MultiVisualOdometry:
         self.lib.hso_vo_multi_alg_bytes(self.h, out.ctypes.data, 5)
         return dict(zip(("frame", "track", "match", "pose", "seed"), [float(x) for x in out]))
 
+    def ba_launches(self):
+        """hso_vo_multi_ba_launches: (kernels the bank's Levenberg loops have enqueued, the k_ba_rounds launches among them)"""
+        out = np.zeros(2, np.int64)
+        self._check(self.lib.hso_vo_multi_ba_launches(self.h, out.ctypes.data), "ba_launches")
+        return int(out[0]), int(out[1])
+
     def call_counts(self):
         calls = np.zeros(16, np.int64); items = np.zeros(16, np.int64)
         n = self.lib.hso_vo_multi_call_counts(self.h, calls.ctypes.data, items.ctypes.data, 16)
@@ -251,13 +269,15 @@ class VisualOdometry:
         self._check(self.lib.hso_vo_trace_state(self.h, 1 if state else 0), "trace_state")
         self._check(self.lib.hso_vo_trace(self.h, path.encode() if path else None), "trace")
 
-    def set_options(self, sync_previous=False, track_no_coop=False, no_numa_pin=False, device_select=False, rectify=False, resize=False):
+    def set_options(self, sync_previous=False, track_no_coop=False, no_numa_pin=False, device_select=False, rectify=False, resize=False, ba_fused=False):
         """rectify: the images handed over from now on are raw and the engine rectifies them on the device (hso_vo_options.rectify).
         resize: they may have any one size per call (sensor images); the engine resizes them to the camera's size on the device, in
-        front of the rectification (hso_vo_options.resize).  depth images stay camera-size."""
+        front of the rectification (hso_vo_options.resize).  depth images stay camera-size.
+        ba_fused: local BA runs a window's Levenberg rounds in one launch (hso_vo_options.ba_fused); same results."""
         o = VoOptions(C.sizeof(VoOptions), int(bool(sync_previous)), int(bool(track_no_coop)), int(bool(no_numa_pin)), int(bool(device_select)))
         o.rectify = int(bool(rectify))
         o.resize = int(bool(resize))
+        o.ba_fused = int(bool(ba_fused))
         self._check(self.lib.hso_vo_set_options(self.h, C.byref(o)), "set_options")
 
     def set_first_frame(self, img, depth_z, timestamp=0.0, T_f_w=None):

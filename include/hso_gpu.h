@@ -105,6 +105,9 @@ typedef struct hso_gpu_options {
                                   0 (default): an upload builds pyramid + statistics only and the images of a frame are written the
                                   first time an entry point that reads them names it (candidate detection, hso_gpu_frame_download_sobel);
                                   results are the same bits either way.  Takes effect for uploads after the call. */
+  int32_t ba_fused;            /* 1: the Levenberg rounds of the local-BA entry points (hso_gpu_ba_optimize, _optimize_multi, _local_multi,
+                                  hso_gpu_seq_local_ba) run in one launch per call, one workgroup per window (k_ba_rounds), instead of
+                                  up to eleven kernels per round; results are the same bits either way */
 } hso_gpu_options;
 int hso_gpu_configure(hso_gpu_ctx* ctx, const hso_gpu_options* options);
 /* The host side of the batched entry points (staging tens of megabytes of local-BA windows, checking and staging map patches) is a

@@ -65,6 +65,11 @@ enum { HSO_BAW_SIZES = 0, HSO_BAW_VERTEX_ROWS = 1, HSO_BAW_FIXED = 2, HSO_BAW_ED
        HSO_BAW_EDGE_CHI2 = 6, HSO_BAW_POSES_OUT = 7, HSO_BAW_POSES_IN = 8, HSO_BAW_IDIST_IN = 9, HSO_BAW_N = 10 };
 int hso_gpu_seq_ba_debug_window(hso_gpu_ctx* ctx, int job, int what, void* out, size_t bytes);
 
+/* test hook: which kernel shape the context's local-BA calls ran.  out[0]: kernels the Levenberg loop has enqueued on this context so
+ * far (the rounds' kernels: not the Huber deltas, not the resident windows' assembly and write-back); out[1]: the k_ba_rounds launches
+ * among them (hso_gpu_options.ba_fused; 0 without it). */
+int hso_gpu_ba_debug_launches(hso_gpu_ctx* ctx, int64_t out[2]);
+
 /* test hook: Gaussian pyramid level `level` of a resident frame (cv::pyrDown chain) and its Scharr derivative image
  * (interleaved Ix, Iy); either output may be NULL */
 int hso_gpu_klt_debug_level(hso_gpu_ctx* ctx, int64_t frame, int level, uint8_t* img_out, int16_t* deriv_out);

@@ -64,7 +64,8 @@ typedef struct hso_vo_options {
                                  depth_z stays indexed by the pixels of the Frame (the camera's size).  A recorded sequence's frame_upload
                                  records hold the resized image.  0: an image of another size is refused.  hso_vo_set_options returns
                                  HSO_E_UNSUPPORTED when the device library lacks the entry; set it before the first frame */
-  int32_t reserved[1];
+  int32_t ba_fused;           /* 1: local bundle adjustment runs a window's Levenberg rounds in one launch (hso_gpu_options.ba_fused: one
+                                 workgroup per window instead of up to eleven kernels per round); same results: tests compare */
 } hso_vo_options;
 int hso_vo_set_options(hso_vo* vo, const hso_vo_options* options);
 /* first keyframe: features are detected the way the initialisation detects them and every feature with
@@ -138,6 +139,10 @@ int hso_vo_multi_get_trajectory(hso_vo_multi* m, int sequence, double* timestamp
  * [9] every other call (the detector, the depth filter's previous-frame pass, the two-view initialisation's KLT: one call per
  * step, an item per sequence in its second stage).  Returns the number of kinds. */
 int hso_vo_multi_call_counts(hso_vo_multi* m, int64_t* calls, int64_t* items, int cap);
+/* which kernel shape the bank's local BA ran (hso_vo_options.ba_fused): out[0] = kernels its Levenberg loops have enqueued so far, out[1] =
+ * the one-launch-per-call kernels among them (hso_gpu_ba_debug_launches of the bank's context); HSO_E_UNSUPPORTED when the device
+ * library has no such entry */
+int hso_vo_multi_ba_launches(hso_vo_multi* m, int64_t out[2]);
 /* The host side of a bank is a small thread pool (per-sequence bookkeeping between the device calls).  A process that runs several
  * banks side by side (one thread each, independent sequences shard freely within a GPU too) says so BEFORE it creates them: every
  * bank then sizes its pool to max(1, (7 * cpu quota) / (2 * LOCAL_WORLD_SIZE * banks_in_process)) workers (3.5 x oversubscribed: most
