@@ -54,7 +54,8 @@ def test_device_chain_follows_the_restatement_frame_by_frame(orc, max_fts):
         worst["rot"] = max(worst["rot"], _rot_err(qa, qb)); worst["trans"] = max(worst["trans"], float(np.linalg.norm(ta - tb)))
         worst["matches"] = max(worst["matches"], abs(a.n_matches - b.n_matches)); worst["trials"] = max(worst["trials"], abs(a.n_trials - b.n_trials))
         worst["cands"] = max(worst["cands"], abs(a.n_candidates - b.n_candidates)); worst["seeds"] = max(worst["seeds"], abs(a.n_seeds - b.n_seeds))
-        assert a.used_inverse == b.used_inverse and a.n_features == b.n_features or abs(a.n_features - b.n_features) <= 3, k
+        assert a.used_inverse == b.used_inverse and (a.n_features == b.n_features or abs(a.n_features - b.n_features) <= 3), \
+            (k, a.used_inverse, b.used_inverse, a.n_features, b.n_features)
     print("device engine vs restatement engine over %d frames at %d features:" % (n - 1, max_fts), worst)
     # the two states stay together: poses within the tracker's / optimiser's tolerances accumulated over the run, the list-driven
     # counters within a handful (a matcher decision inside its stated margin moves one candidate, never a keyframe or a whole list)
