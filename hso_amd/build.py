@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(CSRC, "libhso_gpu.so")
 SOURCES = ["hso_ctx.hip", "hso_frame.hip", "hso_tracker.hip", "hso_tracker_coop.hip", "hso_align.hip", "hso_pose.hip", "hso_ba.hip",
            "hso_seed.hip", "hso_activate.hip", "hso_fast.hip", "hso_edgelet.hip", "hso_select.hip", "hso_klt.hip", "hso_octree.cpp", "hso_octree_dev.hip",
-           "hso_rectify_host.cpp", "hso_rectify.hip"]
+           "hso_rectify_host.cpp", "hso_rectify.hip", "hso_export.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 # Per-file additions.  The tracker megakernel is compiled without LLVM's SLP vectoriser: the packed fp32 / packed 16-bit

@@ -139,6 +139,12 @@ REPROJ_FRAME_DTYPE = np.dtype([("cur_frame_id", "<i8"), ("q", "<f8", 4), ("t", "
                                ("point_count", "<i4"), ("pad_", "<i4")])
 assert REPROJ_FRAME_DTYPE.itemsize == 96
 assert (KF_DTYPE.itemsize, OBS_DTYPE.itemsize, MAP_POINT_DTYPE.itemsize, REPROJ_POINT_DTYPE.itemsize) == (80, 72, 72, 32)
+# records of the map export (hso_point_export, hso_seed_export)
+POINT_EXPORT_DTYPE = np.dtype([("pos", "<f8", 3), ("point", "<i4"), ("keyframe_id", "<i4"), ("n_obs", "<i4"), ("color", "u1"), ("type", "u1"),
+                               ("ftr_type", "u1"), ("pad_", "u1")])
+SEED_EXPORT_DTYPE = np.dtype([("pos", "<f8", 3), ("mu", "<f4"), ("sigma2", "<f4"), ("slot", "<i4"), ("group", "<i4"), ("color", "u1"), ("type", "u1"),
+                              ("level", "u1"), ("pad_", "u1"), ("pad2_", "<i4")])
+assert (POINT_EXPORT_DTYPE.itemsize, SEED_EXPORT_DTYPE.itemsize) == (40, 48)
 
 
 class PoseFeat(C.Structure):
@@ -383,6 +389,8 @@ def load():
     lib.hso_gpu_seed_table_observe_previous.argtypes = [vp, P(Camera), i32, vp, P(SeedFrame), i32, C.c_double, vp, vp]
     lib.hso_gpu_seed_table_observe_previous_begin.argtypes = [vp, P(Camera), i32, vp, P(SeedFrame), i32, C.c_double]
     lib.hso_gpu_seed_table_observe_previous_end.argtypes = [vp, i32, vp, i32]
+    lib.hso_gpu_seqmap_export_points.argtypes = [vp, vp, i32, C.c_uint32, i32, vp, i32, vp]
+    lib.hso_gpu_seed_table_export.argtypes = [vp, i32, vp, i32, vp, i32, vp]
     lib.hso_gpu_seed_reproject_match.argtypes = [vp, P(Camera), i64, P(SE3), C.c_double, vp, i32, i32, i32, vp, vp]
     lib.hso_gpu_fast_detect.argtypes = [vp, i64, i32, i32, i32, vp, i32, P(i32)]
     lib.hso_gpu_fast_detect_batch.argtypes = [vp, P(i64), i32, i32, i32, i32, vp, i32, vp]
@@ -429,6 +437,7 @@ EXPORTED_SYMBOLS = [
     "hso_gpu_rectify_build_map", "hso_gpu_rectify_host", "hso_gpu_rectify_map_create", "hso_gpu_rectify_map_create_tables",
     "hso_gpu_rectify_map_destroy", "hso_gpu_frame_upload_rectified", "hso_gpu_frame_upload_batch_rectified",
     "hso_gpu_frame_upload_batch_resized", "hso_gpu_klt_track_multi",
+    "hso_gpu_seqmap_export_points", "hso_gpu_seed_table_export",
 ]
 
 
@@ -1059,6 +1068,47 @@ class Context:
         out = (Seed * max(n, 1))()
         self._check(self.lib.hso_gpu_seed_table_read(self.h, table, first, n, C.cast(out, C.c_void_p)), "seed_table_read")
         return out
+
+    def seqmap_export_points(self, maps, type_mask=0x18, min_obs=1, cap=None, out=None):
+        """hso_gpu_seqmap_export_points: the selected point rows of the maps, in call order, rows ascending ->
+        (POINT_EXPORT_DTYPE records written, begin [len(maps) + 1], status HSO_OK or E_TRUNCATED).  cap = None: the size query first,
+        then exactly that many; otherwise one call with `cap` (and `out`, a POINT_EXPORT_DTYPE array of at least cap records, if given)."""
+        maps = np.ascontiguousarray(maps, np.int32)
+        begin = np.zeros(len(maps) + 1, np.int32)
+
+        def call(o, c):
+            rc = self.lib.hso_gpu_seqmap_export_points(self.h, _ptr(maps) if len(maps) else None, len(maps), int(type_mask), int(min_obs),
+                                                       _ptr(o) if c > 0 else None, c, _ptr(begin))
+            if rc != E_TRUNCATED:
+                self._check(rc, "seqmap_export_points")
+            return rc
+        if cap is None:
+            call(None, 0)
+            cap = int(begin[-1])
+        if out is None:
+            out = np.zeros(max(cap, 1), POINT_EXPORT_DTYPE)
+        rc = call(out, int(cap))
+        return out[:min(int(cap), int(begin[-1]))], begin, rc
+
+    def seed_table_export(self, table, groups=None, cap=None, out=None):
+        """hso_gpu_seed_table_export: the live seeds of the named groups (None: all), slots ascending ->
+        (SEED_EXPORT_DTYPE records written, the full count, status HSO_OK or E_TRUNCATED); cap / out as in seqmap_export_points"""
+        grp = np.ascontiguousarray(groups, np.int32) if groups is not None else None
+        n = np.zeros(1, np.int32)
+
+        def call(o, c):
+            rc = self.lib.hso_gpu_seed_table_export(self.h, table, (_ptr(grp) if len(grp) else _ptr(np.zeros(1, np.int32))) if grp is not None else None,
+                                                    len(grp) if grp is not None else 0, _ptr(o) if c > 0 else None, c, _ptr(n))
+            if rc != E_TRUNCATED:
+                self._check(rc, "seed_table_export")
+            return rc
+        if cap is None:
+            call(None, 0)
+            cap = int(n[0])
+        if out is None:
+            out = np.zeros(max(cap, 1), SEED_EXPORT_DTYPE)
+        rc = call(out, int(cap))
+        return out[:min(int(cap), int(n[0]))], int(n[0]), rc
 
     def klt_track(self, frame_prev, frame_cur, px_prev, px_init, params=None):
         """initialization::trackKlt's device part between two resident frames -> KLT_RESULT_DTYPE array."""

@@ -1099,6 +1099,16 @@ void hso_seqmap_ba_set_pose(hso_gpu_ctx* ctx, int map, int row, const hso_se3& T
   if (!m->kfs_stale) { m->kfs_stale = true; ctx->seqmaps->stale_kfs.push_back(map); }
 }
 
+// hso_gpu_seqmap_export_points (hso_export.hip): a map's point and observation tables as the device holds them and the library's
+// own keyframe table (the export resolves the frames itself: a keyframe whose frame has left the device is no error there)
+int hso_seqmap_export_view(hso_gpu_ctx* ctx, int map, const hso_map_point** pts, int* n_pts, const hso_obs** obs, int* n_obs, const hso_kf** kfs, int* n_kfs)
+{
+  SeqMap* m = seqmap_of(ctx, map);
+  if (!m) return hso_fail(ctx, HSO_E_INVALID, "seqmap_export_points: no such map");
+  *pts = m->d_pts; *n_pts = (int)m->n_pts; *obs = m->d_obs; *n_obs = (int)m->n_obs; *kfs = m->kfs.data(); *n_kfs = (int)m->kfs.size();
+  return HSO_OK;
+}
+
 // the new frame's table needs room for max_fts rows in both buffers (before any view is taken)
 int hso_seqmap_chain_reserve(hso_gpu_ctx* ctx, int map, int rows)
 {

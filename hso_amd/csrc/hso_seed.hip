@@ -1051,6 +1051,19 @@ int hso_seed_table_rows(hso_gpu_ctx* ctx, int table, const int32_t* slots, int n
   return HSO_OK;
 }
 
+// hso_gpu_seed_table_export (hso_export.hip): every slot of the table — a null `ref_base` marks an erased one, the group sits at
+// *group_offset — after the depth filter's own stream has drained
+int hso_seed_table_export_view(hso_gpu_ctx* ctx, int table, const char** rows, size_t* stride, size_t* seed_offset, size_t* group_offset, int* n_slots,
+                               int* max_group, PyrGeom* g)
+{
+  if (int rc = hso_seed_async_quiesce(ctx)) return rc;
+  SeedTable* t = seed_table_of(ctx, table);
+  if (!t) return hso_fail(ctx, HSO_E_INVALID, "seed_table_export: no such table");
+  *rows = reinterpret_cast<const char*>(t->d); *stride = sizeof(SeedDev); *seed_offset = offsetof(SeedDev, s); *group_offset = offsetof(SeedDev, frame);
+  *n_slots = (int)t->n; *max_group = t->max_group; *g = t->g;
+  return HSO_OK;
+}
+
 template <typename T> static int grow_dev(hso_gpu_ctx* ctx, T** p, size_t* cap, size_t need, size_t keep)
 {
   return hso_dev_grow_keep(ctx, p, cap, need, keep, std::max(need, *cap * 2 + 1024));

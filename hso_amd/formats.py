@@ -10,6 +10,8 @@
                       line, "stamp tx ty tz qx qy qz qw" of T_f_w^-1 (the TUM trajectory format)
   read_trajectory, ate_rmse   the evaluation side: closed-form alignment (Umeyama) + RMSE of positions
   save_snapshot / load_snapshot   the map state in the C-ABI's table layouts, one .npz
+  save_ply / load_ply  the exported map (capi.POINT_EXPORT_DTYPE / SEED_EXPORT_DTYPE records) as a binary little-endian PLY
+                      point cloud: what Viewer::DrawMapRegionPoints draws (src/viewer.cpp:109-136), for any point-cloud viewer
 
 Host-side plumbing: nothing here touches the GPU.
 """
@@ -278,3 +280,66 @@ def load_snapshot(path):
         seeds = (capi.Seed * (len(raw) // C.sizeof(capi.Seed))).from_buffer_copy(raw)
     return dict(camera=cam, keyframes=kfs, images=[z["image_%d" % k] for k in range(len(kfs))], points=z["points"],
                 observations=z["observations"], seeds=seeds, meta=ast.literal_eval(z["meta"].tobytes().decode()))
+
+
+# ---- the exported map as a point cloud.  Binary little-endian PLY: x y z as float64 (the map's own precision), the grey value
+# repeated as red green blue, then whichever of `type` (uchar), `n_obs` (int) and `sigma2` (float) the records carry.
+_PLY_EXTRA = (("type", "uchar", "u1"), ("n_obs", "int", "<i4"), ("sigma2", "float", "<f4"))
+_PLY_TYPES = {"double": "<f8", "float": "<f4", "uchar": "u1", "int": "<i4"}
+
+
+def ply_header(n, extra=()):
+    """the exact header text save_ply writes for n vertices with the extra properties named in `extra`"""
+    lines = ["ply", "format binary_little_endian 1.0", "comment hso_amd map export", "element vertex %d" % n,
+             "property double x", "property double y", "property double z", "property uchar red", "property uchar green", "property uchar blue"]
+    lines += ["property %s %s" % (ply, name) for name, ply, _ in _PLY_EXTRA if name in extra]
+    return "\n".join(lines + ["end_header"]) + "\n"
+
+
+def save_ply(path, records):
+    """records: a structured array with `pos` [n, 3] and `color` (capi.POINT_EXPORT_DTYPE, capi.SEED_EXPORT_DTYPE: what
+    vo.VisualOdometry.map_points / .seeds return).  -> the vertex table written (the array load_ply gives back)."""
+    records = np.asarray(records)
+    extra = [e for e in _PLY_EXTRA if e[0] in (records.dtype.names or ())]
+    dt = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("red", "u1"), ("green", "u1"), ("blue", "u1")] + [(name, np_t) for name, _, np_t in extra])
+    v = np.zeros(len(records), dt)
+    if len(records):
+        v["x"], v["y"], v["z"] = records["pos"][:, 0], records["pos"][:, 1], records["pos"][:, 2]
+        v["red"] = v["green"] = v["blue"] = records["color"]
+        for name, _, _ in extra:
+            v[name] = records[name]
+    with open(path, "wb") as f:
+        f.write(ply_header(len(v), [e[0] for e in extra]).encode("ascii"))
+        f.write(v.tobytes())
+    return v
+
+
+def load_ply(path):
+    """a binary little-endian PLY with one `vertex` element of scalar properties (what save_ply writes) -> structured array, one
+    field per property"""
+    data = open(path, "rb").read()
+    end = data.find(b"end_header\n")
+    if not data.startswith(b"ply\n") or end < 0:
+        raise ValueError("not a PLY file: %s" % path)
+    n, fields, fmt = None, [], None
+    for line in data[:end].decode("ascii").split("\n")[1:]:
+        t = line.split()
+        if not t or t[0] == "comment":
+            continue
+        if t[0] == "format":
+            fmt = t[1]
+        elif t[0] == "element":
+            if t[1] != "vertex" or n is not None:
+                raise ValueError("only a single vertex element is read")
+            n = int(t[2])
+        elif t[0] == "property":
+            if len(t) != 3 or t[1] not in _PLY_TYPES:
+                raise ValueError("unsupported PLY property: %s" % line)
+            fields.append((t[2], _PLY_TYPES[t[1]]))
+    if fmt != "binary_little_endian" or n is None:
+        raise ValueError("only binary little-endian PLY files with a vertex element are read")
+    dt = np.dtype(fields)
+    body = data[end + len(b"end_header\n"):]
+    if len(body) != n * dt.itemsize:
+        raise ValueError("PLY body holds %d bytes, the header promises %d" % (len(body), n * dt.itemsize))
+    return np.frombuffer(body, dt).copy()

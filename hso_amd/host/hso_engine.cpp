@@ -310,6 +310,58 @@ int Bank::trajectory(int k, double* stamps, hso_se3* T_f_w, int cap) const
   return n;
 }
 
+bool Bank::export_available()
+{
+  return hso_gpu_seqmap_export_points && hso_gpu_seed_table_export;
+}
+
+// Viewer::DrawMapRegionPoints' set (src/viewer.cpp:109-136) straight from the resident maps.  A point's id is its row, so the
+// records need no translation.  The device selects by the rows' own state words; what the engine adds is that a row its tables no
+// longer hold is dropped: a sequence that was started again keeps its map handle, and rows of the earlier run stay on the device
+// behind (or between) the rows the new run has patched.
+int Bank::map_points(int k, uint32_t type_mask, int min_obs, hso_point_export* out, int cap, int32_t* begin)
+{
+  if (k >= size() || cap < 0 || !begin || (cap > 0 && !out)) throw Refused("get_map_points: bad argument");
+  std::vector<int> who;
+  for (int i = 0; i < size(); i++) if (k < 0 || i == k) who.push_back(i);
+  flush_maps(who);                                                // a step ends with it; after set_first_frame or a refused image rows may be pending
+  std::vector<int32_t> maps, dev_begin(who.size() + 1, 0);
+  size_t rows = 0;
+  for (int i : who) {
+    int n_points = 0;
+    check(hso_gpu_seqmap_size(ctx_, seq_[i]->map, nullptr, &n_points, nullptr), "Map");
+    maps.push_back(seq_[i]->map);
+    rows += (size_t)n_points;
+  }
+  if (rows > (size_t)std::numeric_limits<int32_t>::max()) throw Refused("get_map_points: more than 2^31 - 1 rows");
+  std::vector<hso_point_export> all(rows);
+  check(hso_gpu_seqmap_export_points(ctx_, maps.data(), (int)maps.size(), type_mask, min_obs, all.data(), (int)rows, dev_begin.data()), "Map export");
+  size_t n = 0;
+  for (size_t w = 0; w < who.size(); w++) {
+    const Seq& s = *seq_[who[w]];
+    begin[w] = (int32_t)n;
+    for (int32_t r = dev_begin[w]; r < dev_begin[w + 1]; r++) {
+      const hso_point_export& e = all[(size_t)r];
+      if ((size_t)e.point >= s.points.size() || s.points[(size_t)e.point].kind == kPtDeleted) continue;
+      if (n < (size_t)cap) out[n] = e;
+      n++;
+    }
+  }
+  begin[who.size()] = (int32_t)n;
+  return n > (size_t)cap ? HSO_E_TRUNCATED : HSO_OK;
+}
+
+// the depth filter's live seeds as the resident table holds them (the library waits for an idle-time pass in flight); a seed's
+// group is its sequence's index
+int Bank::live_seeds(int k, hso_seed_export* out, int cap, int32_t* n)
+{
+  if (k >= size() || cap < 0 || !n || (cap > 0 && !out)) throw Refused("get_seeds: bad argument");
+  const int32_t group = k;
+  const int rc = hso_gpu_seed_table_export(ctx_, seed_table_, k < 0 ? nullptr : &group, k < 0 ? 0 : 1, out, cap, n);
+  if (rc != HSO_E_TRUNCATED) check(rc, "DepthFilter export");
+  return rc;
+}
+
 // the frames the sequences dropped since the last call leave the device: one call, one wait
 void Bank::release_queued()
 {

@@ -179,6 +179,12 @@ public:
   int keyframes(int k, double* stamps, hso_se3* T_f_w, int32_t* frame_ids, int cap) const;
   // every frame the sequence has processed since its start: (timestamp, T_f_w as it stood when the frame was finished)
   int trajectory(int k, double* stamps, hso_se3* T_f_w, int cap) const;
+  // The map as the device holds it (hso_gpu_seqmap_export_points / hso_gpu_seed_table_export), between steps: sequence k, or every
+  // sequence in index order for k < 0.  Rows pending in the host mirror are flushed first.  begin: 2 entries for one sequence,
+  // size() + 1 for all.  Return HSO_OK or HSO_E_TRUNCATED (the counts are exact either way); the caller checks export_available().
+  int map_points(int k, uint32_t type_mask, int min_obs, hso_point_export* out, int cap, int32_t* begin);
+  int live_seeds(int k, hso_seed_export* out, int cap, int32_t* n);
+  static bool export_available();    // the device library linked in has the two export entries
   bool trace(int k, const char* path);
   bool trace_state(int k, bool on);
   // rectify: throws Refused for a camera the reference does not rectify; the caller checks rectify_available() first

@@ -151,6 +151,42 @@ int hso_vo_multi_get_trajectory(hso_vo_multi* m, int sequence, double* timestamp
   return m->bank->trajectory(sequence, timestamps, T_f_w, cap);
 }
 int hso_vo_get_trajectory(hso_vo* v, double* timestamps, hso_se3* T_f_w, int cap) { return v ? v->bank->trajectory(0, timestamps, T_f_w, cap) : HSO_E_INVALID; }
+// the map export: answered before anything is touched when the device library has no such entries; HSO_E_TRUNCATED leaves the handle
+// as usable as HSO_OK does
+static int export_points(Bank* b, int sequence, uint32_t type_mask, int min_obs, hso_point_export* out, int cap, int32_t* begin)
+{
+  if (!Bank::export_available()) { if (!b->poisoned) b->err = "get_map_points: the device library has no map export (hso_gpu_seqmap_export_points)"; return HSO_E_UNSUPPORTED; }
+  int rc = HSO_OK;
+  const int g = guarded(b, [&]() { rc = b->map_points(sequence, type_mask, min_obs, out, cap, begin); });
+  return g < 0 ? g : rc;
+}
+static int export_seeds(Bank* b, int sequence, hso_seed_export* out, int cap, int32_t* n)
+{
+  if (!Bank::export_available()) { if (!b->poisoned) b->err = "get_seeds: the device library has no map export (hso_gpu_seed_table_export)"; return HSO_E_UNSUPPORTED; }
+  int rc = HSO_OK;
+  const int g = guarded(b, [&]() { rc = b->live_seeds(sequence, out, cap, n); });
+  return g < 0 ? g : rc;
+}
+int hso_vo_get_map_points(hso_vo* v, uint32_t type_mask, int min_obs, hso_point_export* out, int cap, int32_t* n)
+{
+  if (!v || !n) return HSO_E_INVALID;
+  int32_t begin[2] = {0, 0};
+  const int rc = export_points(v->bank, 0, type_mask, min_obs, out, cap, begin);
+  if (rc == HSO_OK || rc == HSO_E_TRUNCATED) *n = begin[1];
+  return rc;
+}
+int hso_vo_get_seeds(hso_vo* v, hso_seed_export* out, int cap, int32_t* n) { return (v && n) ? export_seeds(v->bank, 0, out, cap, n) : HSO_E_INVALID; }
+int hso_vo_multi_get_map_points(hso_vo_multi* m, int sequence, uint32_t type_mask, int min_obs, hso_point_export* out, int cap, int32_t* begin)
+{
+  if (!m || !begin || sequence >= m->bank->size()) return HSO_E_INVALID;
+  return export_points(m->bank, sequence < 0 ? -1 : sequence, type_mask, min_obs, out, cap, begin);
+}
+int hso_vo_multi_get_seeds(hso_vo_multi* m, int sequence, hso_seed_export* out, int cap, int32_t* n)
+{
+  if (!m || !n || sequence >= m->bank->size()) return HSO_E_INVALID;
+  return export_seeds(m->bank, sequence < 0 ? -1 : sequence, out, cap, n);
+}
+
 int hso_vo_multi_ba_launches(hso_vo_multi* m, int64_t out[2])
 {
   if (!m || !out) return HSO_E_INVALID;

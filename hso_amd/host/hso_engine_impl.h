@@ -31,6 +31,11 @@ extern "C" int hso_gpu_frame_download_level(hso_gpu_ctx* ctx, int64_t frame_id, 
 // hso_gpu_klt_track call per sequence
 extern "C" int hso_gpu_klt_track_multi(hso_gpu_ctx* ctx, const hso_klt_pair* pairs, int n_pairs, const float* px_prev, const float* px_init, int n_total,
                                        const hso_klt_params* params, hso_klt_result* out) __attribute__((weak));
+// the map export (hso_vo_get_map_points / hso_vo_get_seeds): without the entries (tests/fakegpu) the calls answer HSO_E_UNSUPPORTED
+extern "C" int hso_gpu_seqmap_export_points(hso_gpu_ctx* ctx, const int32_t* maps, int n_maps, uint32_t type_mask, int min_obs, hso_point_export* out,
+                                            int cap, int32_t* begin_out) __attribute__((weak));
+extern "C" int hso_gpu_seed_table_export(hso_gpu_ctx* ctx, int table, const int32_t* groups, int n_groups, hso_seed_export* out, int cap,
+                                         int32_t* n_out) __attribute__((weak));
 
 namespace hso {
 namespace engine {

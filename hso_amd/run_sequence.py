@@ -17,6 +17,9 @@ Options (the reference's `key=value` style, test_dataset.cpp:66-114):
   gt=<trajectory file>     ground truth in the same format: prints the ATE (RMSE after similarity alignment)
   trace=<path>             record every device call of the run (trace_frames=<n>: only of the first n frames)
   times=1                  print per-frame wall time
+  cloud=<path.ply>         write the map's points at the end of the run (hso_vo_get_map_points: the set and the colours of
+                           Viewer::DrawMapRegionPoints, src/viewer.cpp:109-136) as a binary PLY point cloud
+  seeds=<path.ply>         the same for the depth filter's live seeds (hso_vo_get_seeds), the semi-dense layer
 
 Layout of a sequence folder = the reference's: <folder>/*.png (or .pgm), one stamp per line in the stamp file."""
 import os
@@ -110,6 +113,11 @@ def main(argv, return_line=False):
     formats.write_trajectory(result, rows)
     line = {"frames": end - start, "keyframes": len(rows), "frames_per_s": (len(t_frames) - 1) / max(sum(t_frames[1:]), 1e-9),
             "tracking_failures": n_fail, "init_frames": n_init, "result": result}
+    for key, fetch in (("cloud", odo.map_points), ("seeds", odo.seeds)):
+        if key in opt:
+            os.makedirs(os.path.dirname(os.path.abspath(opt[key])), exist_ok=True)
+            line[key] = opt[key]
+            line["n_" + key] = len(formats.save_ply(opt[key], fetch()))
     if "gt" in opt:
         (es, exyz, _), (gs, gxyz, _) = formats.read_trajectory(result), formats.read_trajectory(opt["gt"])
         common = [s_ for s_ in es if s_ in set(gs)]

@@ -99,6 +99,10 @@ def _declare(lib):
     lib.hso_vo_host_cpu_quota.argtypes = []
     lib.hso_vo_multi_get_trajectory.argtypes = [vp, i32, vp, vp, i32]
     lib.hso_vo_get_trajectory.argtypes = [vp, vp, vp, i32]
+    lib.hso_vo_get_map_points.argtypes = [vp, C.c_uint32, i32, vp, i32, vp]
+    lib.hso_vo_get_seeds.argtypes = [vp, vp, i32, vp]
+    lib.hso_vo_multi_get_map_points.argtypes = [vp, i32, C.c_uint32, i32, vp, i32, vp]
+    lib.hso_vo_multi_get_seeds.argtypes = [vp, i32, vp, i32, vp]
     return lib
 
 
@@ -123,7 +127,22 @@ EXPORTED_SYMBOLS = ["hso_vo_create", "hso_vo_destroy", "hso_vo_last_error", "hso
                     "hso_vo_multi_create", "hso_vo_multi_destroy", "hso_vo_multi_last_error", "hso_vo_multi_size",
                     "hso_vo_multi_set_first_frames", "hso_vo_multi_add_images", "hso_vo_multi_get_status", "hso_vo_multi_get_keyframes",
                     "hso_vo_multi_call_counts", "hso_vo_host_share", "hso_vo_multi_alg_bytes", "hso_vo_multi_threads", "hso_vo_host_cpu_quota", "hso_vo_multi_start", "hso_vo_multi_trace", "hso_vo_multi_add_images_device", "hso_vo_multi_get_trajectory", "hso_vo_get_trajectory", "hso_vo_trace_state", "hso_vo_multi_trace_state", "hso_vo_set_options", "hso_vo_multi_set_options",
-                    "hso_vo_multi_ba_launches"]
+                    "hso_vo_multi_ba_launches", "hso_vo_get_map_points", "hso_vo_get_seeds", "hso_vo_multi_get_map_points", "hso_vo_multi_get_seeds"]
+
+VIEWER_TYPE_MASK = (1 << 3) | (1 << 4)   # TYPE_UNKNOWN | TYPE_GOOD: the points Viewer::DrawMapRegionPoints meets (src/viewer.cpp:109-136)
+
+
+def _export(call, dtype, n_counts, check, what):
+    """the size query (cap = 0, out = NULL), then the records: call(out, cap, counts) -> status; -> (records, counts)"""
+    counts = np.zeros(n_counts, np.int32)
+    rc = call(None, 0, counts.ctypes.data)
+    if rc != capi.E_TRUNCATED:
+        check(rc, what)
+    out = np.zeros(int(counts[-1]), dtype)
+    if len(out):
+        check(call(out.ctypes.data, len(out), counts.ctypes.data), what)
+    return out, counts
+
 
 CALL_KINDS = ["frame_upload", "frame_release", "track", "reproject_select_pose", "align", "pose", "seed_observe", "seed_activate", "ba", "other"]
 
@@ -220,6 +239,16 @@ class MultiVisualOdometry:
         self.lib.hso_vo_multi_get_trajectory(self.h, k, ts.ctypes.data, T.ctypes.data, n)
         return ts[:n], T[:n]
 
+    def map_points(self, k=-1, type_mask=VIEWER_TYPE_MASK, min_obs=1):
+        """hso_vo_multi_get_map_points: sequence k's points, or (k = -1) every sequence's in one device call ->
+        (capi.POINT_EXPORT_DTYPE records, begin): records begin[i] .. begin[i + 1] are sequence i's (two entries for one sequence)"""
+        return _export(lambda out, cap, cnt: self.lib.hso_vo_multi_get_map_points(self.h, int(k), int(type_mask), int(min_obs), out, cap, cnt),
+                       capi.POINT_EXPORT_DTYPE, self.n + 1 if k < 0 else 2, self._check, "get_map_points")
+
+    def seeds(self, k=-1):
+        """hso_vo_multi_get_seeds: the live seeds of sequence k (-1: of every sequence; `group` names the sequence) -> capi.SEED_EXPORT_DTYPE records"""
+        return _export(lambda out, cap, cnt: self.lib.hso_vo_multi_get_seeds(self.h, int(k), out, cap, cnt), capi.SEED_EXPORT_DTYPE, 1, self._check, "get_seeds")[0]
+
     def alg_bytes(self):
         out = np.zeros(5)
         self.lib.hso_vo_multi_alg_bytes(self.h, out.ctypes.data, 5)
@@ -308,6 +337,15 @@ class VisualOdometry:
         ts = np.zeros(max(n, 1)); T = (capi.SE3 * max(n, 1))(); ids = np.zeros(max(n, 1), np.int32)
         self.lib.hso_vo_get_keyframes(self.h, capi._ptr(ts), C.cast(T, C.c_void_p), capi._ptr(ids), n)
         return [(float(ts[i]), T[i], int(ids[i])) for i in range(n)]
+
+    def map_points(self, type_mask=VIEWER_TYPE_MASK, min_obs=1):
+        """hso_vo_get_map_points: the map's points (default: the viewer's set) as capi.POINT_EXPORT_DTYPE records, rows ascending"""
+        return _export(lambda out, cap, cnt: self.lib.hso_vo_get_map_points(self.h, int(type_mask), int(min_obs), out, cap, cnt),
+                       capi.POINT_EXPORT_DTYPE, 1, self._check, "get_map_points")[0]
+
+    def seeds(self):
+        """hso_vo_get_seeds: the depth filter's live seeds as capi.SEED_EXPORT_DTYPE records, slots ascending"""
+        return _export(lambda out, cap, cnt: self.lib.hso_vo_get_seeds(self.h, out, cap, cnt), capi.SEED_EXPORT_DTYPE, 1, self._check, "get_seeds")[0]
 
 
 def init_compute_matrix(f_ref, f_cur, focal_length, reproj_thresh=2.0):

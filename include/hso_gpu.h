@@ -917,6 +917,48 @@ int hso_gpu_seqmap_patch_lists(hso_gpu_ctx* ctx, const hso_seqmap_list_patch* pa
 int hso_gpu_seqmap_patch_links(hso_gpu_ctx* ctx, int map, const int32_t* obs_ids, const int32_t* obs_point, int n_obs);
 int hso_gpu_seqmap_set_key_points(hso_gpu_ctx* ctx, int map, const int32_t* key_points /* 5 * n_kfs */, int n_kfs);
 
+/* ---- map export: what the reference's one consumer of the map reads, Viewer::DrawMapRegionPoints (src/viewer.cpp:109-136: for every
+ *      keyframe and every feature with a point, point->pos_ drawn in point->color_), and, as the semi-dense layer, the depth filter's
+ *      live seeds at the position the upgrade loop would give them (src/depth_filter.cpp:440-460).  The tables are indexed by the
+ *      caller's ids and mostly dead rows after a long run: rows are selected, coloured and packed on the device (hso_export.hip: three
+ *      short launches — count per chunk of rows, one workgroup's scan, emit) and only the selected records come back.
+ *      Selection: a point row is exported when the type nibble of its state word is non-zero and bit `type` of type_mask is set,
+ *      HSO_PT_BAD is clear and obs_count >= min_obs (the viewer's set: min_obs = 1, type_mask = 1 << TYPE_UNKNOWN | 1 << TYPE_GOOD =
+ *      0x18); rows never patched read as type 0 and drop out.  A seed slot is exported when it is live, its group is named and mu is
+ *      finite and > 0.
+ *      Order: maps in call order, rows ascending inside a map (begin_out[i] .. begin_out[i + 1] are map i's records); slots ascending.
+ *      Capacity: begin_out / n_out always report what the call WOULD write.  When that exceeds cap the first cap records are
+ *      written, nothing beyond them, and the call returns HSO_E_TRUNCATED; cap == 0 with out == NULL is the size query.
+ *      Colour: the first observation of the point's chain (obs_begin, hso_obs.pad_, at most obs_count steps) whose kf == host_kf
+ *      gives level-0 byte ((int)px[1], (int)px[0]) of that keyframe's resident frame (src/depth_filter.cpp:459); 128 (Point::color_'s
+ *      initial value, include/hso/point.h:121) when there is no such observation, when the keyframe row is out of range, when its
+ *      frame is not resident, or for a pixel outside the image.  A seed's colour is the same lookup in its host frame at its own px.
+ *      ONE DIFFERENCE from the reference: it colours only the points born from seeds and leaves the points of the two-view
+ *      initialisation at 128; here every point with a host observation is coloured.
+ *      HSO_E_INVALID (nothing is queued): an unknown map / table, n_maps < 0 or > 65535, cap < 0, out == NULL with cap > 0, a NULL
+ *      begin_out / n_out, a negative group. ---- */
+typedef struct hso_point_export {   /* 40 B */
+  double pos[3];        /* Point::pos_ as the map holds it (copied, not recomputed) */
+  int32_t point;        /* row in the sequence map = the caller's point id */
+  int32_t keyframe_id;  /* hso_kf.keyframe_id of the host keyframe; -1: host_kf is outside the keyframe table */
+  int32_t n_obs;        /* obs_count */
+  uint8_t color;
+  uint8_t type, ftr_type;   /* the two nibbles of HSO_PT_KEY */
+  uint8_t pad_;
+} hso_point_export;
+int hso_gpu_seqmap_export_points(hso_gpu_ctx* ctx, const int32_t* maps, int n_maps, uint32_t type_mask, int min_obs, hso_point_export* out,
+                                 int cap, int32_t* begin_out /* n_maps + 1 */);
+typedef struct hso_seed_export {    /* 48 B */
+  double pos[3];        /* T_ref_w^-1 * (f * (1 / mu)) in fp64: the expression of depth_filter.cpp's upgrade loop */
+  float mu, sigma2;
+  int32_t slot, group;
+  uint8_t color, type, level, pad_;
+  int32_t pad2_;
+} hso_seed_export;
+/* groups == NULL: every group.  Waits for an idle-time pass in flight like every other seed-table entry point. */
+int hso_gpu_seed_table_export(hso_gpu_ctx* ctx, int table, const int32_t* groups /* NULL = all */, int n_groups, hso_seed_export* out, int cap,
+                              int32_t* n_out);
+
 #define HSO_SEQ_MAX_VISIT 24
 #define HSO_SEQ_MAX_KFS 2048      /* rows of a sequence map's keyframe table the chain accepts (the reference keeps Config::maxNKfs() = 2000) */
 #define HSO_SEQ_MAX_COVIS 8

@@ -99,6 +99,18 @@ int hso_vo_get_keyframes(hso_vo* vo, double* timestamps, hso_se3* T_f_w, int32_t
  * harness gathers (BASELINE configs[4]); returns the number of frames, fills at most cap */
 int hso_vo_get_trajectory(hso_vo* vo, double* timestamps, hso_se3* T_f_w, int cap);
 
+/* The map beside the trajectory: what Viewer::DrawMapRegionPoints draws (src/viewer.cpp:109-136) and, as the semi-dense layer, the
+ * depth filter's live seeds — selected, coloured and packed on the device from the resident tables (include/hso_gpu.h:
+ * hso_gpu_seqmap_export_points, hso_gpu_seed_table_export; selection, order, colour and the capacity rule are stated there).  Valid
+ * between steps; rows pending in the engine's mirror are flushed first, and the seed call waits for an idle-time pass in flight.
+ * The viewer's set is type_mask = 0x18 (TYPE_UNKNOWN | TYPE_GOOD), min_obs = 1.  hso_point_export.point is the engine's point id;
+ * hso_seed_export.group is the sequence's index in its bank (0 for a single handle).  A row left over from before a restart of the
+ * sequence (hso_vo_start on a running handle) is not exported.  *n: what the call would write; when that exceeds cap the first cap
+ * records are written and HSO_E_TRUNCATED is returned (the handle stays usable); cap = 0 with out = NULL asks for the size.
+ * HSO_E_UNSUPPORTED (nothing touched) when the device library has no export entries. */
+int hso_vo_get_map_points(hso_vo* vo, uint32_t type_mask, int min_obs, hso_point_export* out, int cap, int32_t* n);
+int hso_vo_get_seeds(hso_vo* vo, hso_seed_export* out, int cap, int32_t* n);
+
 /* ---- N independent sequences over one device context, in lockstep (hso_amd/host/hso_engine*.cpp): BASELINE north_star
  * "independent sequences ... batched"; configs[4] = what test/euroc_batch.sh:9-18 runs one after the other.  One step takes one
  * image per sequence and runs every stage ONCE for all of them: hso_gpu_frame_upload_batch, hso_gpu_seq_chain (the tracker's reference tables,
@@ -134,6 +146,13 @@ int hso_vo_multi_set_options(hso_vo_multi* m, const hso_vo_options* options);
 int hso_vo_multi_get_status(hso_vo_multi* m, int sequence, hso_vo_status* st);
 int hso_vo_multi_get_keyframes(hso_vo_multi* m, int sequence, double* timestamps, hso_se3* T_f_w, int32_t* frame_ids, int cap);
 int hso_vo_multi_get_trajectory(hso_vo_multi* m, int sequence, double* timestamps, hso_se3* T_f_w, int cap);
+/* hso_vo_get_map_points / hso_vo_get_seeds for one sequence of the bank, or for all of them in ONE device call (sequence = -1:
+ * sequences in index order).  begin: records begin[i] .. begin[i + 1] belong to sequence i — hso_vo_multi_size() + 1 entries for
+ * sequence = -1, two entries (0 and the count) for a single sequence.  The seed call reports one count; the records name their
+ * sequence in `group`. */
+int hso_vo_multi_get_map_points(hso_vo_multi* m, int sequence /* -1: all */, uint32_t type_mask, int min_obs, hso_point_export* out, int cap,
+                                int32_t* begin);
+int hso_vo_multi_get_seeds(hso_vo_multi* m, int sequence /* -1: all */, hso_seed_export* out, int cap, int32_t* n);
 /* batched C-ABI calls issued so far and the per-sequence requests they carried, per kind: [0] frame upload, [1] frame release,
  * [2] tracker, [3] reprojection + matching, [4] matching alone, [5] pose, [6] seed observation, [7] seed activation, [8] local BA,
  * [9] every other call (the detector, the depth filter's previous-frame pass, the two-view initialisation's KLT: one call per
